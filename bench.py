@@ -10,7 +10,18 @@ Workload (BASELINE.json configs[1]): lego.json, 100k synthetic lego-like
 Gaussians (the lego PLY in the reference is a git-LFS pointer),
 n_grid 128 (--n_grid override), jelly as written.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed warm-up steps, times K steps, and prints
+the headline line (value, ms_per_step, the configuration).  --dump-outputs DIR
+then also writes the last timed step's outputs (render-space means and
+covariances, image, radii) as DIR/<name>.npy; the scene is seeded, so two
+builds run with the same arguments can be compared array for array.  --full
+adds every measurement that takes GPU (or CPU) runs of its own: the sim /
+render breakdown, the per-kernel and roofline figures, configs B' / C / D / E
+(other_configs), the CPU baseline, and for N > 1 the side measurements
+(multi_gpu); --no-cpu-baseline, --no-extra-configs, --no-multi-configs and
+--multi-configs trim what --full runs.
 
 Multi-GPU (torch.distributed.run, one rank per GPU), two modes for the
 headline line:
@@ -27,7 +38,7 @@ headline line:
   particles migrate between slabs every 10 substeps; the frame's means/covs
   are gathered to rank 0, which renders it.  value = scene particles x
   substeps / time.
-Either way an N > 1 line also carries `multi_gpu`: north_star's slab
+Either way an N > 1 line under --full also carries `multi_gpu`: north_star's slab
 sharding measured on lego and on config D (bicycle 1M, 256^3) with the
 render-aware re-cut (rank 0 renders the gathered frame and takes the
 particle share sim / (sim + render)), per-rank sim ms, rank-0 render and
@@ -64,9 +75,18 @@ def parse():
     ap.add_argument("--config", default="lego.json")
     ap.add_argument("--material", default=None, help="override (e.g. metal) -- not the headline config")
     ap.add_argument("--no-render", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement (the sim / render breakdown, the "
+                         "per-kernel and roofline figures, configs B' / C / D / E, the CPU baseline; N > 1: "
+                         "multi_gpu) and add their fields to the JSON line; off: set up, warm up, time the steps, "
+                         "print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the frame's render-space "
+                         "means and covariances, its image and radii) as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all: a fixed seeded sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the driver-timed config C (metal) / D (bicycle 1M, 256^3) side runs")
+                    help="--full: skip the driver-timed config C (metal) / D (bicycle 1M, 256^3) side runs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--multi", choices=("dp", "slab"), default="slab",
                     help="N > 1 headline: slab = one lego scene sharded by spatial slab over RCCL (default, "
@@ -122,6 +142,26 @@ def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> device tensor) as
+    path/<name>.npy in float32.  The arrays share DUMP_BUDGET_BYTES equally;
+    one above its share is written as a fixed sample of its flattened elements
+    (indices drawn once from a generator seeded with 0, sorted), so two runs
+    with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def launch_ranks(n):
@@ -530,7 +570,8 @@ def slab_exchange_bytes(sim):
     return sum(16 * w * ny * nz for (_, ny, _, nz) in sim.engine.slab_rects() if ny > 0 and nz > 0)
 
 
-def slab_frames(args, dev, rank, world, xp, barrier, red_dev, cfg, n, ng, frames=3, warmup=6, weighted=True):
+def slab_frames(args, dev, rank, world, xp, barrier, red_dev, cfg, n, ng, frames=3, warmup=6, weighted=True,
+                last=None):
     """One scene sharded by slab over the N ranks, frame by frame as main.py
     runs it (step, postprocess, gather to rank 0, rank 0 renders), with the
     render-aware re-cut: rank 0 measures its simulation and render times and
@@ -542,7 +583,8 @@ def slab_frames(args, dev, rank, world, xp, barrier, red_dev, cfg, n, ng, frames
     around its step call), its particle count, the bytes it sends per substep
     in the window exchange, its migrations, and rank 0's render and gather
     host times (the gather includes the wait for the slowest rank's
-    simulation)."""
+    simulation).  last: a dict that receives rank 0's last frame (the gathered
+    means and covariances, the image and the radii)."""
     import copy
     import torch
     import torch.distributed as dist
@@ -575,9 +617,12 @@ def slab_frames(args, dev, rank, world, xp, barrier, red_dev, cfg, n, ng, frames
         m, c = sim.gather_world(*w_args, render_space=True)
         g1 = time.perf_counter()
         if rank == 0:
-            acc["K"], _, _ = raster.forward(m, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg, cam.height,
-                                            cam.width, tx, ty, sh_degree=3, shs=feats, cov3D_precomp=c)
+            acc["K"], image, radii = raster.forward(m, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
+                                                    cam.height, cam.width, tx, ty, sh_degree=3, shs=feats,
+                                                    cov3D_precomp=c)
             torch.cuda.current_stream().synchronize()
+            if last is not None:
+                last.update(means=m, covs=c, image=image, radii=radii)
         g2 = time.perf_counter()
         e1.synchronize()
         if timed:
@@ -845,8 +890,11 @@ def slab_main(args, dev, rank, world, red_dev):
         dist.barrier()
         torch.cuda.synchronize()
 
+    last = {} if args.dump_outputs and rank == 0 else None
     r = slab_frames(args, dev, rank, world, xp, barrier, red_dev, args.config, args.particles, args.n_grid,
-                    frames=args.steps, warmup=max(2, args.warmup))
+                    frames=args.steps, warmup=max(2, args.warmup), last=last)
+    if last:
+        dump_outputs(args.dump_outputs, last)
     spf = r["substeps_per_frame"]
     out = {"metric": METRIC, "value": r["particle_substeps_per_s"], "unit": "particle-substeps/s",
            "n_gpus": world, "steps": args.steps, "warmup": max(2, args.warmup), "ms_per_step": r["frame_ms"],
@@ -857,7 +905,7 @@ def slab_main(args, dev, rank, world, red_dev):
                       "material": "jelly", "parallelism": f"slab{world}"},
            "substeps_per_s": spf * 1e3 / r["frame_ms"], "frames_per_s": 1e3 / r["frame_ms"],
            "num_rendered": r["num_rendered"], "slab": r}
-    if not args.no_multi_configs and not args.no_extra_configs:
+    if args.full and not args.no_multi_configs and not args.no_extra_configs:
         out["multi_gpu"] = multi_gpu_configs(args, dev, rank, world, xp, barrier, red_dev)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -932,7 +980,7 @@ def main():
     # slab side measurements (multi_gpu) in either mode
     slab = world > 1 and args.multi == "slab"
     xp = None
-    if slab or (world > 1 and not args.no_multi_configs and not args.no_extra_configs):
+    if slab or (world > 1 and args.full and not args.no_multi_configs and not args.no_extra_configs):
         from gsmpm.dist import make_transport
         xp = make_transport(rank, world, device=dev)
     scene = build_scene(args, dev, rank=0 if slab else rank)
@@ -952,6 +1000,7 @@ def main():
     # device tensors would stall the host on the whole frame)
     w_scale, w_center = float(scene["s"]), [float(v) for v in scene["c"].reshape(-1).tolist()]
     state = {"t": 0.0, "K": 0}
+    keep_last = bool(args.dump_outputs) and rank == 0  # state["last"]: the newest frame's outputs, for --dump-outputs
 
     host_t = [] if os.environ.get("GSMPM_BENCH_HOST_TIMING") else None  # per-call host time (diagnostic)
 
@@ -983,11 +1032,14 @@ def main():
             render_stream.wait_event(ev)
             if delay_cycles:
                 torch.cuda._sleep(delay_cycles)
-            K, _, _ = raster.forward(means_r, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
-                                     cam.height, cam.width, tanx, tany, sh_degree=3, shs=feats, cov3D_precomp=covs_r)
+            K, image, radii = raster.forward(means_r, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
+                                             cam.height, cam.width, tanx, tany, sh_degree=3, shs=feats,
+                                             cov3D_precomp=covs_r)
         means_r.record_stream(render_stream)  # allocated on the simulator's stream
         covs_r.record_stream(render_stream)
         state["K"] = K
+        if keep_last:
+            state["last"] = {"means": means_r, "covs": covs_r, "image": image, "radii": radii}
 
     # --render-async: the forward with the pair count left on the device
     # (gsmpm_raster_forward_async), enqueued right behind the frame's
@@ -1027,14 +1079,17 @@ def main():
         if ren_async:
             for ar, m, c in aq:
                 nr, flags = ar.result()
+                image, radii = ar.color, ar.radii
                 if flags:  # the synchronous form renders it (counted in the frame's time)
-                    state["K"], _, _ = raster.forward(m, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
-                                                      cam.height, cam.width, tanx, tany, sh_degree=3, shs=feats,
-                                                      cov3D_precomp=c)
+                    state["K"], image, radii = raster.forward(m, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center,
+                                                              bg, cam.height, cam.width, tanx, tany, sh_degree=3,
+                                                              shs=feats, cov3D_precomp=c)
                     acap["reissued"] += 1
                     acap["cap"] = max(acap["cap"], int(ar.counts[0]) + int(ar.counts[0]) // 4 + 4096)
                 else:
                     state["K"] = nr
+                if keep_last:
+                    state["last"] = {"means": m, "covs": c, "image": image, "radii": radii}
             aq.clear()
             return
         if rq is not None:
@@ -1097,10 +1152,12 @@ def main():
                 t.append(time.perf_counter())
             elif not args.render_overlap and means_r is not None:  # main.py's order, one stream
                 t.append(time.perf_counter())
-                K, _, _ = raster.forward(means_r, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
-                                         cam.height, cam.width, tanx, tany, sh_degree=3, shs=feats,
-                                         cov3D_precomp=covs_r)
+                K, image, radii = raster.forward(means_r, opac, cam.view_mat, cam.full_proj_mat, cam.cam_center, bg,
+                                                 cam.height, cam.width, tanx, tany, sh_degree=3, shs=feats,
+                                                 cov3D_precomp=covs_r)
                 state["K"] = K
+                if keep_last:
+                    state["last"] = {"means": means_r, "covs": covs_r, "image": image, "radii": radii}
                 t.append(time.perf_counter())
             else:
                 ev = torch.cuda.Event()
@@ -1128,11 +1185,11 @@ def main():
     # k_render's and the whole forward's in-frame times: three events per
     # forward on its own stream (gsmpm_raster_set_timing), read after the
     # timed region; no host wait is added inside it
-    time_render = not args.no_render and rank == 0
+    time_render = args.full and not args.no_render and rank == 0
     if time_render:
         raster.timing()
         raster.set_timing(True)
-    esc0 = sim.escapes() if hasattr(sim, "escapes") else None  # (a sync, outside the timed region)
+    esc0 = sim.escapes() if args.full and hasattr(sim, "escapes") else None  # (a sync, outside the timed region)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         frame()
@@ -1148,7 +1205,7 @@ def main():
                                "forward_ms": round(fw_ms / n_fw, 4)}
     # particle scatters that left their chunk window so far (fused pipeline; a diagnostic of the
     # re-binning interval: gsmpm_mpm_escapes)
-    escapes = sim.escapes() if (world == 1 and hasattr(sim, "escapes")) else None
+    escapes = sim.escapes() if (args.full and world == 1 and hasattr(sim, "escapes")) else None
     escapes_timed = None if escapes is None or esc0 is None else escapes - esc0
     if rq is not None:  # the render worker's last frame is done (flush): stop it
         rq.put(None)
@@ -1168,6 +1225,61 @@ def main():
             n_total = int(nt.item())
     else:
         n_total = n_local
+
+    if keep_last:
+        last = state.get("last")
+        if last is None:  # --no-render: the frame's outputs are the simulator's
+            means_r, covs_r = sim.world_outputs(w_scale, w_center, render_space=True)
+            last = {"means": means_r, "covs": covs_r}
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, last)
+
+    out = {
+        "metric": METRIC,
+        "value": n_total * spf * args.steps / elapsed,
+        "unit": "particle-substeps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if slab else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (lego-like Gaussians, seed 0; lego PLY is an LFS pointer in the reference)",
+        "config": {"workload": f"{args.config} frame: {spf} substeps + postprocess + render "
+                               f"{cam.width}x{cam.height} SH3", "particles_per_gpu": n_local,
+                   "particles_total": n_total, "n_grid": sa.n_grid, "material": sa.material,
+                   "substep_dt": dt, "render_overlap": bool(args.render_overlap),
+                   "render_cus": render_cus_actual if masked_render_stream is not None else None,
+                   "render_cu_layout": args.render_cu_layout if masked_render_stream is not None else None,
+                   "render_delay_us": args.render_delay_us if args.render_overlap else None,
+                   "render_first": bool(args.render_first) if args.render_overlap else None,
+                   "render_thread": bool(rq is not None),
+                   "render_async": ren_async,
+                   "render_async_pairs_cap": acap["cap"] if ren_async else None,
+                   "render_async_reissued": acap["reissued"] if ren_async else None,
+                   "parallelism": (f"slab{world}" if slab else f"dp{world} independent scenes") if world > 1
+                   else "single"},
+        "substeps_per_s": spf * args.steps / elapsed,
+        "frames_per_s": args.steps / elapsed,
+        "num_rendered": state["K"],
+        "rebin": sim.rebin_state() if hasattr(sim, "rebin_state") else None,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if slab:  # the simulator's captured graphs hold RCCL work: destroy them before the communicator
+            sim.engine.close()
+        if xp is not None:
+            barrier()
+            xp.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:  # the plain run ends here: every measurement below takes GPU runs of its own
+        return finish()
 
     # ---- breakdown (untimed by the contract; measured on the same stream) ----
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -1232,35 +1344,7 @@ def main():
         kern = {k: kms[i] for i, k in enumerate(names)}
         abytes = {k: v for k, v in algorithmic_bytes(n_local, sa.n_grid, sa.material).items() if k in kern}
 
-    out = {
-        "metric": METRIC,
-        "value": n_total * spf * args.steps / elapsed,
-        "unit": "particle-substeps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if slab else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (lego-like Gaussians, seed 0; lego PLY is an LFS pointer in the reference)",
-        "config": {"workload": f"{args.config} frame: {spf} substeps + postprocess + render "
-                               f"{cam.width}x{cam.height} SH3", "particles_per_gpu": n_local,
-                   "particles_total": n_total, "n_grid": sa.n_grid, "material": sa.material,
-                   "substep_dt": dt, "render_overlap": bool(args.render_overlap),
-                   "render_cus": render_cus_actual if masked_render_stream is not None else None,
-                   "render_cu_layout": args.render_cu_layout if masked_render_stream is not None else None,
-                   "render_delay_us": args.render_delay_us if args.render_overlap else None,
-                   "render_first": bool(args.render_first) if args.render_overlap else None,
-                   "render_thread": bool(rq is not None),
-                   "render_async": ren_async,
-                   "render_async_pairs_cap": acap["cap"] if ren_async else None,
-                   "render_async_reissued": acap["reissued"] if ren_async else None,
-                   "parallelism": (f"slab{world}" if slab else f"dp{world} independent scenes") if world > 1
-                   else "single"},
-        "substeps_per_s": spf * args.steps / elapsed,
-        "frames_per_s": args.steps / elapsed,
+    out.update({
         "sim_ms_per_frame": sim_ms,
         "sim_substeps_per_s": spf / (sim_ms / 1e3),
         "render_ms_per_frame": render_ms,
@@ -1268,13 +1352,12 @@ def main():
         "render_default_stream_first_ms": render_cold_ms,
         # per forward of the timed frames, on the render's stream beside the simulator
         "render_in_frame": render_in_frame,
-        "num_rendered": state["K"],
         # particle scatters that left their chunk window (each makes the next k_grid_f sweep every tile):
         # since set_particles, and in the timed frames
         "escapes_since_start": escapes,
         "escapes_timed": escapes_timed,
         "rebin": sim.rebin_state() if hasattr(sim, "rebin_state") else None,
-    }
+    })
     if kern is not None:
         # dominant kernel: the one with the most time per frame among those that
         # carry the reference's work
@@ -1329,15 +1412,7 @@ def main():
         out["config"]["rank0_window_rects"] = sim.engine.slab_rects()
         out["config"]["slab_bounds"] = sim.bounds  # after any re-cuts (gsmpm_mpm_slab_set_rebalance, on by default)
         out["config"]["slab_recuts"] = sim.rebalances
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if slab:  # the simulator's captured graphs hold RCCL work: destroy them before the communicator
-        sim.engine.close()
-    if xp is not None:
-        barrier()
-        xp.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

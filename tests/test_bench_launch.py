@@ -49,6 +49,35 @@ def test_default_is_one_rank():
     assert out["n_gpus"] == 1 and out["config"]["parallelism"] == "single"
 
 
+def test_full_and_dump_outputs_flags_parse():
+    out = _line(_run(["--full", "--dump-outputs", "unused", "--dry-run"]))
+    assert out["n_gpus"] == 1 and out["dry_run"] is True
+
+
+def test_dump_outputs_float32_and_seeded_sample(tmp_path, monkeypatch):
+    """dump_outputs writes <name>.npy in float32; an array above its share of
+    the byte budget is written as the same sorted sample of its elements on
+    every call, and the files stay within the budget."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("gsmpm_bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 2 * 1000)  # 1000 elements per array
+    big = torch.arange(30_000, dtype=torch.float64).reshape(100, 300)
+    small = torch.arange(12, dtype=torch.int32).reshape(4, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (1000,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a.max() > 20_000 and np.all(a == np.round(a))  # a spread of big's elements
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+    assert a.nbytes + s.nbytes <= 4 * 2 * 1000
+
+
 def test_launcher_rank_count_must_match_flag():
     p = _run(["--gpus", "8", "--dry-run"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0

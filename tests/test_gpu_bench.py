@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--no-extra-configs", *extra]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--no-extra-configs", *extra]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -45,6 +45,40 @@ def test_bench_line_contract_and_render_thread():
     assert d0["num_rendered"] == d["num_rendered"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline only (nothing that takes a
+    run of its own), --steps is the number of timed steps, and --dump-outputs
+    writes the last timed frame as float32 .npy files within 64 MB: the
+    frame's render-space means / covariances (one row per simulated
+    particle), the 800x800 image and the radii."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+              "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["unit"] == "particle-substeps/s" and d["higher_is_better"] is True
+    # value and ms_per_step describe the same 3 timed steps of 100 substeps
+    n = d["config"]["particles_total"]
+    assert abs(d["value"] - n * 100 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "kernels_roofline", "kernels_ms_per_launch", "sim_ms_per_frame", "render_ms_per_frame",
+              "render_in_frame", "other_configs", "cpu_baseline", "multi_gpu"):
+        assert k not in d, k
+    arrs = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert set(arrs) == {"means", "covs", "image", "radii"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert arrs["means"].shape == (n, 3) and arrs["covs"].shape == (n, 6) and arrs["radii"].shape == (n,)
+    assert arrs["image"].shape == (3, 800, 800) and arrs["image"].max() > 0
+    assert (arrs["radii"] > 0).sum() > 0 and d["num_rendered"] > 0
+
+
 def test_bench_two_ranks_on_one_gpu_multi_fields():
     """--gpus 2 rehearsed on one GPU (GSMPM_SHARE_GPU=1: both ranks on cuda:0,
     RCCL over its socket transport): the default slab headline (one lego
@@ -54,7 +88,7 @@ def test_bench_two_ranks_on_one_gpu_multi_fields():
     and the side measurements: the replicas form (one scene per rank) and the
     sim / render split."""
     env = dict(os.environ, GSMPM_SHARE_GPU="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "3", "--full",
            "--multi-configs", "dp,split"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -8,7 +8,7 @@ set -o pipefail
 O=${1:-gpurun_out/ab_esc}; mkdir -p $O
 run() {  # name lib args...
   local name=$1 lib=$2; shift 2
-  GSMPM_LIB=$PWD/gaussian-splatting-mpm_amd/$lib timeout -k 10 150 python3 bench.py --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
+  GSMPM_LIB=$PWD/gaussian-splatting-mpm_amd/$lib timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/${name}.json')); print('$name', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), d['kernels_ms_per_launch'], 'esc', d.get('escapes_timed'))"
 }
 for rep in $(seq 1 ${REPS:-2}); do

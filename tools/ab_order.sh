@@ -5,7 +5,7 @@ set -o pipefail
 O=${1:-gpurun_out/ab_order}; mkdir -p $O
 run() {  # name order args...
   local name=$1 ord=$2; shift 2
-  GSMPM_CHUNK_ORDER=$ord timeout -k 10 150 python3 bench.py --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
+  GSMPM_CHUNK_ORDER=$ord timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/${name}.json')); print('$name', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), d['kernels_ms_per_launch'], 'esc', d.get('escapes_timed'))"
 }
 for rep in $(seq 1 ${REPS:-2}); do

@@ -8,7 +8,7 @@ O=${1:-gpurun_out/ab_rebin}; mkdir -p $O
 G=$PWD/gaussian-splatting-mpm_amd
 one() {  # one <name> <lib> <auto> <bench args...>
   local n=$1 L=$2 A=$3; shift 3
-  GSMPM_REBIN_AUTO=$A GSMPM_LIB=$L timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5 "$@" > $O/$n.json 2> $O/$n.err || return 1
+  GSMPM_REBIN_AUTO=$A GSMPM_LIB=$L timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5 "$@" > $O/$n.json 2> $O/$n.err || return 1
   python3 -c "import json; d=json.load(open('$O/$n.json')); print('$n', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), 'esc_timed', d['escapes_timed'], d['rebin'])"
 }
 for rep in $(seq 1 ${REPS:-2}); do

@@ -8,7 +8,7 @@ timeout -k 10 700 python3 -u -m pytest -x -q --timeout 300 --timeout-method thre
 tail -1 $O/tests.txt
 run() {  # name env-value args...
   local name=$1 f=$2; shift 2
-  GSMPM_REBIN_FORK=$f timeout -k 10 150 python3 bench.py --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
+  GSMPM_REBIN_FORK=$f timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --no-extra-configs "$@" > $O/${name}.json 2> $O/${name}.err || { tail -5 $O/${name}.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/${name}.json')); print('$name', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), d['kernels_ms_per_launch'])"
 }
 for rep in 1 2 3; do

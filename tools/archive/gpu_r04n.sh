@@ -6,7 +6,7 @@ O=gpurun_out/r04n
 mkdir -p $O
 for i in 1 2 3; do for nr in 0 1; do
   a=""; [ $nr -eq 1 ] && a="--no-render"
-  timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 $a > $O/nr_${nr}_$i.json 2> $O/nr_${nr}_$i.err || exit 1
+  timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 $a > $O/nr_${nr}_$i.json 2> $O/nr_${nr}_$i.err || exit 1
   python3 -c "import json; d=json.load(open('$O/nr_${nr}_$i.json')); print('no_render=$nr', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4))"
 done; done | tee $O/ab_norender.txt
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/r04s
 mkdir -p $O
 for i in 1 2 3; do for rt in 0 1; do
-  timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 --render-thread $rt > $O/rt_${rt}_$i.json 2> $O/rt_${rt}_$i.err || { tail -5 $O/rt_${rt}_$i.err; exit 1; }
+  timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 --render-thread $rt > $O/rt_${rt}_$i.json 2> $O/rt_${rt}_$i.err || { tail -5 $O/rt_${rt}_$i.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/rt_${rt}_$i.json')); print('render_thread=$rt', round(d['value']/1e9,4), 'ms/frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), 'K', d['num_rendered'])"
 done; done | tee $O/ab_render_thread.txt
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -5,6 +5,6 @@ set -o pipefail
 O=gpurun_out/r04v
 mkdir -p $O
 for n in 2 4; do
-  GSMPM_SHARE_GPU=1 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29590 + n)) bench.py --gpus $n --steps 5 --warmup 2 > $O/slab_$n.json 2> $O/slab_$n.err || { tail -20 $O/slab_$n.err; exit 1; }
+  GSMPM_SHARE_GPU=1 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29590 + n)) bench.py --full --gpus $n --steps 5 --warmup 2 > $O/slab_$n.json 2> $O/slab_$n.err || { tail -20 $O/slab_$n.err; exit 1; }
   tail -c 700 $O/slab_$n.json; echo
 done

@@ -18,6 +18,6 @@ cat $O/grid_f_phases.txt
 REPS=2 bash tools/ab_r05.sh $O/cus "thread||" "spread16||GSMPM_BENCH_RENDER_CUS=16" \
   "low16||GSMPM_BENCH_RENDER_CUS=16 GSMPM_BENCH_RENDER_CU_LAYOUT=low" "xmajor16||GSMPM_BENCH_RENDER_CUS=16 GSMPM_BENCH_RENDER_CU_LAYOUT=xmajor" \
   "low8||GSMPM_BENCH_RENDER_CUS=8 GSMPM_BENCH_RENDER_CU_LAYOUT=low" "xmajor8||GSMPM_BENCH_RENDER_CUS=8 GSMPM_BENCH_RENDER_CU_LAYOUT=xmajor" || exit 1
-GSMPM_SHARE_GPU=1 timeout -k 10 600 python3 bench.py --gpus 2 --steps 5 --warmup 2 --multi-configs lego,split \
+GSMPM_SHARE_GPU=1 timeout -k 10 600 python3 bench.py --full --gpus 2 --steps 5 --warmup 2 --multi-configs lego,split \
   > $O/rehearsal_2ranks.json 2> $O/rehearsal_2ranks.err || { tail -20 $O/rehearsal_2ranks.err; exit 1; }
 tail -1 $O/rehearsal_2ranks.json | cut -c1-1500

@@ -6,7 +6,7 @@ set -o pipefail
 TAG=${1:-r06final}
 O=gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1 || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1 || exit 1
 tail -c 300 $O/bench.log; echo
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --no-extra-configs --no-cpu-baseline --steps 50 --warmup 5 > $O/prof.log 2>&1 || exit 1

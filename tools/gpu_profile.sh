@@ -6,7 +6,7 @@ set -e
 TAG=${1:-r03}
 O=gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --no-extra-configs --no-cpu-baseline --steps 20 --warmup 5 > $O/prof.log 2>&1
 f=$(find $O/prof -name 'run_kernel_stats.csv' | head -n 1)

@@ -13,7 +13,7 @@ run_tests() {
 }
 run_bench() {
   [ "$BENCH" = "-" ] && return 0
-  timeout -k 10 400 python3 bench.py $BENCH > $O/bench.log 2>&1
+  timeout -k 10 400 python3 bench.py --full $BENCH > $O/bench.log 2>&1
   local rc=$?; tail -c 400 $O/bench.log; echo; return $rc
 }
 run_prof() {

@@ -9,9 +9,10 @@ for i in 1 2 3; do
     echo "lego tile_dsort=$TD $(tail -n 1 gpurun_out/td/lego.$TD.$i.log)"
   done
 done
+O=${OUT_DIR:-out}/td; mkdir -p $O
 for i in 1 2; do
   for TD in 0 1; do
-    GSMPM_RASTER_TILE_DSORT=$TD timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 > gpurun_out/td/bench.$TD.$i.json 2> gpurun_out/td/bench.$TD.$i.err
-    python3 -c "import json; d=json.load(open('gpurun_out/td/bench.$TD.$i.json')); print('bench tile_dsort=$TD', round(d['value']/1e9,4), 'frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), 'render', round(d['render_ms_per_frame'],4))"
+    GSMPM_RASTER_TILE_DSORT=$TD timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 3 > $O/bench.$TD.$i.json 2> $O/bench.$TD.$i.err
+    python3 -c "import json; d=json.load(open('$O/bench.$TD.$i.json')); print('bench tile_dsort=$TD', round(d['value']/1e9,4), 'frame', round(d['ms_per_step'],4), 'sim', round(d['sim_ms_per_frame'],4), 'render', round(d['render_ms_per_frame'],4))"
   done
 done
