@@ -145,8 +145,9 @@ __device__ __forceinline__ int tile_of(const float (&x)[3], const GridDims& g, c
 // loads + ImpulseBC.apply + compute_stress_from_F_trial for one particle
 template <int MAT>
 __device__ __forceinline__ void particle_front(const Particles& ps, int p, const BcTable* __restrict__ bct,
-                                               uint32_t mask, float dt, const MatConsts& mc, float (&x)[3],
-                                               float (&v)[3], float (&C)[3][3], float& m, float (&nvt)[3][3]) {
+                                               uint32_t mask, float dt, const MatConsts& mc, const MatIds<MAT>& mi,
+                                               float (&x)[3], float (&v)[3], float (&C)[3][3], float& m,
+                                               float (&nvt)[3][3]) {
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     x[d] = ps.ld(PX + d, p);
@@ -173,7 +174,29 @@ __device__ __forceinline__ void particle_front(const Particles& ps, int p, const
   // compute_stress_from_F_trial (utils.py:13-54), fused: stress never leaves registers
 #pragma unroll
   for (int i = 0; i < 9; ++i) nvt[i / 3][i % 3] = 0.f;
-  if constexpr (MAT != 0) {
+  if constexpr (MAT == kMatMixed) {
+    // the per-particle dispatch (constitutive.h): F stored for metal / sand /
+    // foam rows, the yield for metal rows, nvt 0 for jelly-as-written rows
+    float F[3][3], tau[3][3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) F[i / 3][i % 3] = ps.ld(PF + i, p);
+    const int code = material_code(mi.id(p), mi.jelly);
+    float yld = ps.ld(PYLD, p);
+    const float mu = ps.ld(PMU, p), lam = ps.ld(PLAM, p);
+    return_map_and_stress_mixed(code, F, mu, lam, yld, dt, mc, tau);
+    if (code >= 1 && code <= 3) {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) ps.st(PF + i, p, F[i / 3][i % 3]);
+    }
+    if (code == 1) ps.st(PYLD, p, yld);
+    const float nvol = -ps.ld(PVOL, p);
+    if (code != 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) nvt[i][j] = nvol * tau[i][j];
+    }
+  } else if constexpr (MAT != 0) {
     float F[3][3], tau[3][3];
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i / 3][i % 3] = ps.ld(PF + i, p);
@@ -427,88 +450,30 @@ __device__ __forceinline__ void p2g_scatter(unsigned long long* cell0, const flo
 #endif
 }
 
+// The body is p2g_body.inc, included by k_p2g<MAT> (one material: the uniform
+// scenes' symbols, arguments and code, unchanged) and k_p2g_mixed (MAT = 6,
+// the per-particle ids as one more argument).
 template <int MAT>
 __global__ __launch_bounds__(256) void k_p2g(Particles ps, GridDims g, Tiles tl, ChunkIn ck,
                                              const BcTable* __restrict__ bct, uint32_t mask, float dt, MatConsts mc,
                                              float4* __restrict__ slots, float4* __restrict__ gacc,
                                              int* __restrict__ nonfin) {
-  // channel-planar window: a wave's 8-byte atomics to random nodes of one
-  // channel spread over all 64 banks (the node-interleaved float4 layout put
-  // every channel on 16 of them: 75 % of LDS cycles were bank conflicts)
-  __shared__ unsigned long long s_acc[4 * kWin];
-  __shared__ float s_max[4];
-  stamp(0, 0);
-  const int nch = ck.nchunk[0];
-  for (int w = blockIdx.x; w < nch; w += gridDim.x) {
-    const int4 cr = ck.chunk[w];
-    const int t = cr.x, first = cr.y, cnt = cr.z;
-    const int k = threadIdx.x;
-    if (t == tl.ntiles) {
-      // particles outside the grid: bounds-checked global f32 atomics (reference UB region)
-      if (k < cnt) {
-        const int p = ck.list[first + k];
-        float x[3], v[3], C[3][3], m, nvt[3][3];
-        particle_front<MAT>(ps, p, bct, mask, dt, mc, x, v, C, m, nvt);
-        p2g_global<MAT>(x, v, C, m, nvt, g, dt, gacc);
-      }
-      continue;  // workgroup-uniform
-    }
-    const int tx = t / (tl.td * tl.td), ty = (t / tl.td) % tl.td, tz = t % tl.td;
-    for (int q = k; q < kWin * 4; q += kChunk) s_acc[q] = 0ull;
-    float x[3], v[3], C[3][3], m = 0.f, nvt[3][3];
-    int base[3] = {0, 0, 0};
-    float fx[3] = {1.f, 1.f, 1.f}, ww[3][3], dw[3][3];
-    float bound = 0.f;
-    if (k < cnt) {
-      const int p = ck.list[first + k];
-      particle_front<MAT>(ps, p, bct, mask, dt, mc, x, v, C, m, nvt);
-      bspline(x, g.inv_dx, base, fx, ww, dw);
-      {  // non-finite scatter inputs (the fixed-point conversion would hide them; fused.h)
-        float chk = m + v[0] + v[1] + v[2];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) chk += nvt[i / 3][i % 3] + C[i / 3][i % 3];
-        if (!__builtin_isfinite(chk)) *nonfin = 1;
-      }
-      float vm = 0.f, cm = 0.f, sm = 0.f;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        vm = fmaxf(vm, fabsf(v[r]));
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          cm = fmaxf(cm, fabsf(C[r][c]));
-          sm = fmaxf(sm, fabsf(nvt[r][c]));
-        }
-      }
-      // |m v + m C dpos| <= m (|v| + 3 * 1.5 dx |C|), |dt nvt dweight| <= dt * 3 * 1.5 inv_dx |nvt|
-      bound = fmaxf(m, m * (vm + 4.5f * g.dx * cm) + dt * 4.5f * g.inv_dx * sm) * 1.01f;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o));
-    if ((k & 63) == 0) s_max[k >> 6] = bound;
-    __syncthreads();  // also orders the window zeroing before the adds
-    if (w == (int)blockIdx.x) {
-      stamp(0, 2);
-      stamp_val(0, 5, cnt);
-      stamp_val(0, 6, GSMPM_HWREG(4));  // HW_ID
-    }
-    const float bmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    int ebits;
-    frexpf(bmax, &ebits);                     // bmax < 2^ebits
-    // every contribution below 2^50 (to_fixed needs < 2^51); a node sums <= 256 of them
-    const int S = bmax > 0.f ? 50 - ebits : 0;
-    if (k < cnt) {
-      const int l0 = base[0] - tx * kTile, l1 = base[1] - ty * kTile, l2 = base[2] - tz * kTile;
-      p2g_scatter<MAT>(s_acc + ((l0 * kTW + l1) * kTW + l2), fx, ww, dw, v, C, m, nvt, g, dt, ldexp(1.0, S));
-    }
-    __syncthreads();
-    if (w == (int)blockIdx.x) stamp(0, 3);
-    float* dst = reinterpret_cast<float*>(slots + (size_t)w * kWin);
-    for (int q = k; q < kWin * 4; q += kChunk)
-      dst[q] = (float)ldexp((double)(long long)s_acc[(q & 3) * kWin + (q >> 2)], -S);
-    __syncthreads();  // LDS reuse by the next chunk
-    if (w == (int)blockIdx.x) stamp(0, 4);
-  }
-  stamp(0, 1);
+  static_assert(MAT != kMatMixed, "the mixed dispatch is k_p2g_mixed");
+  const MatIds<MAT> mi{};
+#define GSMPM_P2G_BODY_INCLUDER
+#include "p2g_body.inc"
+#undef GSMPM_P2G_BODY_INCLUDER
+}
+
+// k_p2g<6>: each particle's material from its id (constitutive.h)
+__global__ __launch_bounds__(256) void k_p2g_mixed(Particles ps, GridDims g, Tiles tl, ChunkIn ck,
+                                                   const BcTable* __restrict__ bct, uint32_t mask, float dt,
+                                                   MatConsts mc, float4* __restrict__ slots, float4* __restrict__ gacc,
+                                                   int* __restrict__ nonfin, MatIds<kMatMixed> mi) {
+  constexpr int MAT = kMatMixed;
+#define GSMPM_P2G_BODY_INCLUDER
+#include "p2g_body.inc"
+#undef GSMPM_P2G_BODY_INCLUDER
 }
 
 // ------------------------------------------------------------------ grid --
@@ -1278,6 +1243,16 @@ struct InitArgs {
   float density, logE, y, yield0;
 };
 
+// compute_mu_lam_from_E_nu (utils.py:349-362) in f32, from the host's f32
+// log10(E) and logit of nu (model.py:41-44): the one path every mu / lam of a
+// handle takes (k_init, k_region_params), so equal E and nu give equal bits
+__device__ __forceinline__ void mu_lam_of(float logE, float y, float& mu, float& lam) {
+  const float E = powf(10.0f, logE);
+  const float nu = 0.49f / (1.0f + expf(-y));
+  mu = E / (2.0f * (1.0f + nu));
+  lam = E * nu / ((1.0f + nu) * (1.0f - 2.0f * nu));
+}
+
 // MPM_state.__init__ (model.py:100-116) + compute_mu_lam_from_E_nu + mass
 __global__ __launch_bounds__(256) void k_init(Particles ps, InitArgs a) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1303,12 +1278,50 @@ __global__ __launch_bounds__(256) void k_init(Particles ps, InitArgs a) {
   const float vol = a.vol[o];
   ps.st(PVOL, p, vol);
   ps.st(PMASS, p, a.density * vol);
-  // utils.py:349-362 in f32
-  const float E = powf(10.0f, a.logE);
-  const float nu = 0.49f / (1.0f + expf(-a.y));
-  ps.st(PMU, p, E / (2.0f * (1.0f + nu)));
-  ps.st(PLAM, p, E * nu / ((1.0f + nu) * (1.0f - 2.0f * nu)));
+  float mu, lam;
+  mu_lam_of(a.logE, a.y, mu, lam);
+  ps.st(PMU, p, mu);
+  ps.st(PLAM, p, lam);
   ps.st(PYLD, p, a.yield0);
+}
+
+// ---------------------------------------------- per-particle materials --
+__global__ __launch_bounds__(256) void k_fill_f(float* __restrict__ out, int n, float v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = v;
+}
+
+// The box test of the region records: ImpulseBC's own (boundary_conditions.py:44,
+// 60, 84), strict, in f32, on the particle's current position.
+struct RegionBox {
+  float c[3], s[3];
+};
+__device__ __forceinline__ bool in_region(const Particles& ps, int p, const RegionBox& b) {
+  return fabsf(ps.ld(PX + 0, p) - b.c[0]) < b.s[0] && fabsf(ps.ld(PX + 1, p) - b.c[1]) < b.s[1] &&
+         fabsf(ps.ld(PX + 2, p) - b.c[2]) < b.s[2];
+}
+
+// MaterialTypeModifier.apply (boundary_conditions.py:81-85): the id array is in caller order
+__global__ __launch_bounds__(256) void k_region_material(Particles ps, const int* __restrict__ orig, RegionBox b,
+                                                         float material, float* __restrict__ mat) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= ps.n) return;
+  if (in_region(ps, p, b)) mat[orig[p]] = material;
+}
+
+// MaterialParamsModifier.apply / applymu (boundary_conditions.py:57-70) as the
+// reference means them: E, nu and density of the rows inside become mu, lam
+// and mass the way k_init makes them, then mu takes the override
+__global__ __launch_bounds__(256) void k_region_params(Particles ps, RegionBox b, float logE, float y, float density,
+                                                       int has_mu, float mu_over) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= ps.n) return;
+  if (!in_region(ps, p, b)) return;
+  float mu, lam;
+  mu_lam_of(logE, y, mu, lam);
+  ps.st(PMU, p, has_mu ? mu_over : mu);
+  ps.st(PLAM, p, lam);
+  ps.st(PMASS, p, density * ps.ld(PVOL, p));
 }
 
 __global__ __launch_bounds__(256) void k_get(Particles ps, const int* __restrict__ orig, int plane0, int width,
@@ -1448,6 +1461,28 @@ __global__ __launch_bounds__(256) void k_constitutive(const float* __restrict__ 
   }
 }
 
+// k_constitutive with a material value per row (the mixed dispatch, constitutive.h)
+__global__ __launch_bounds__(256) void k_constitutive_mixed(const float* __restrict__ mat, const float* __restrict__ Ft,
+                                                            int n, const float* __restrict__ mu,
+                                                            const float* __restrict__ lam, float* __restrict__ yld,
+                                                            float dt, MatConsts mc, int jelly, float* __restrict__ Fo,
+                                                            float* __restrict__ To) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float F[3][3], tau[3][3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) F[k / 3][k % 3] = Ft[(size_t)i * 9 + k];
+  const int code = material_code(mat[i], jelly);
+  float y = yld[i];
+  return_map_and_stress_mixed(code, F, mu[i], lam[i], y, dt, mc, tau);
+  if (code == 1) yld[i] = y;  // every other row's yield keeps its bits
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    Fo[(size_t)i * 9 + k] = F[k / 3][k % 3];
+    To[(size_t)i * 9 + k] = tau[k / 3][k % 3];
+  }
+}
+
 // filling.py:11-24: floor(x / dx) cell counts (i32 atomics), vol = dx^3 / count
 __global__ __launch_bounds__(256) void k_fill_count(const float* __restrict__ x, int n, int ng, float gdx,
                                                     int* __restrict__ cnt) {
@@ -1486,6 +1521,12 @@ struct gsmpm_mpm {
   MatConsts mc{};
   Tiles tl{};
   int mat_kernel = 0;  // template code of k_p2g
+  // per-particle materials: the id array [np] in caller order (allocated when
+  // the handle first enters mixed mode, holds the ids while `mixed`), and
+  // whether the P2G kernels run the mixed instantiation (until set_particles)
+  float* mat_ids = nullptr;
+  bool mixed = false;
+  bool rebin_set = false;  // the re-binning interval was set by the caller (it survives a mode change)
   int n = 0, np = 0;
   float* planes = nullptr;
   float* cold = nullptr;  // [NCOLD][np] init_cov, cov, R in caller order
@@ -1686,6 +1727,13 @@ static BinOut bin_out(gsmpm_mpm* h, int c) {
 
 static bool use_fused(const gsmpm_mpm* h) { return h->fused; }
 
+// template code of the P2G kernels: the create-time material, or the mixed dispatch
+static int kernel_code(const gsmpm_mpm* h) { return h->mixed ? kMatMixed : h->mat_kernel; }
+// the ids of the mixed kernels: caller order, through the current storage -> caller map
+static MatIds<kMatMixed> mat_ids_of(gsmpm_mpm* h) {
+  return MatIds<kMatMixed>{h->mat_ids, h->orig, (h->prm.flags & GSMPM_FLAG_JELLY_FCR) ? 4 : 0};
+}
+
 // the chunk records k_fused walks: the balanced order (k_chunk_order) or tile order
 // the multi-round XCD placement (k_chunk_order_xcd_seq): its grid must be a multiple of 8
 static bool xcd_seq_on(const gsmpm_mpm* h) {
@@ -1736,8 +1784,12 @@ static void launch(const hipEvent_t* ev, F kernel, dim3 grid, dim3 block, hipStr
 
 template <int MAT>
 static void launch_p2g(gsmpm_mpm* h, int c, uint32_t mask, float dt, hipStream_t st, const hipEvent_t* ev) {
-  launch(ev, k_p2g<MAT>, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
-         (const BcTable*)h->dev_bc, mask, dt, h->mc, h->slots, h->gacc, h->nonfin_dev);
+  if constexpr (MAT == kMatMixed)
+    launch(ev, k_p2g_mixed, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
+           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->slots, h->gacc, h->nonfin_dev, mat_ids_of(h));
+  else
+    launch(ev, k_p2g<MAT>, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
+           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->slots, h->gacc, h->nonfin_dev);
 }
 
 // counts -> list offsets + chunk list, then the per-tile lists
@@ -2104,11 +2156,12 @@ static int substep_begin(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream
     const size_t nn = (size_t)h->g.ng * h->g.ng * h->g.ng;
     GSMPM_HIP(hipMemsetAsync(h->gacc, 0, nn * sizeof(float4), st));
   }
-  switch (h->mat_kernel) {
+  switch (kernel_code(h)) {
     case 0: launch_p2g<0>(h, c, mask, dt, st, e8); break;
     case 1: launch_p2g<1>(h, c, mask, dt, st, e8); break;
     case 2: launch_p2g<2>(h, c, mask, dt, st, e8); break;
     case 3: launch_p2g<3>(h, c, mask, dt, st, e8); break;
+    case kMatMixed: launch_p2g<kMatMixed>(h, c, mask, dt, st, e8); break;
     default: launch_p2g<4>(h, c, mask, dt, st, e8); break;
   }
   GSMPM_LAUNCH_CHECK();
@@ -2232,17 +2285,23 @@ struct FusedLaunch {
 template <int MAT, int MODE>
 static void launch_fused_t(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, const hipEvent_t* ev) {
   const int xlo = h->slab ? h->s_lo - h->s_margin : INT_MIN, xhi = h->slab ? h->s_hi + h->s_margin : INT_MAX;
-  launch(ev, k_fused<MAT, MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl, chunk_in_f(h, f.c),
-         touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots, xlo, xhi,
-         (const FusedRare*)(h->frare_dev + f.c * kRareSlots + f.slot), f.mask_prev);
+  if constexpr (MAT == kMatMixed)
+    launch(ev, k_fused_mixed<MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
+           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
+           xlo, xhi, (const FusedRare*)(h->frare_dev + f.c * kRareSlots + f.slot), f.mask_prev, mat_ids_of(h));
+  else
+    launch(ev, k_fused<MAT, MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
+           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
+           xlo, xhi, (const FusedRare*)(h->frare_dev + f.c * kRareSlots + f.slot), f.mask_prev);
 }
 template <int MODE>
 static void launch_fused_m(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, const hipEvent_t* ev) {
-  switch (h->mat_kernel) {
+  switch (kernel_code(h)) {
     case 0: launch_fused_t<0, MODE>(h, f, st, ev); break;
     case 1: launch_fused_t<1, MODE>(h, f, st, ev); break;
     case 2: launch_fused_t<2, MODE>(h, f, st, ev); break;
     case 3: launch_fused_t<3, MODE>(h, f, st, ev); break;
+    case kMatMixed: launch_fused_t<kMatMixed, MODE>(h, f, st, ev); break;
     default: launch_fused_t<4, MODE>(h, f, st, ev); break;
   }
 }
@@ -2420,6 +2479,50 @@ static int upload_bc(gsmpm_mpm* h) {
   GSMPM_HIP(hipMemcpy(h->dev_bc, &h->host_bc, sizeof(BcTable), hipMemcpyHostToDevice));
   drop_graphs(h);
   return GSMPM_OK;
+}
+
+// Mixed mode (per-particle materials): the P2G kernels take their mixed
+// instantiation, the cached step graphs (which baked the uniform one) are
+// dropped, and the re-binning interval becomes the stress-bearing default.
+// Refused, with nothing launched, where the ids could not follow their
+// particles: a slab's migration payload carries the hot planes only, and
+// the folded pipeline (GSMPM_FOLD=1) is an A/B form without the instantiation.
+// fill: the ids start as the create-time material (region calls).
+static int enter_mixed(gsmpm_mpm* h, const char* who, bool fill, hipStream_t st) {
+  if (h->slab) {
+    set_error(std::string(who) + ": per-particle materials are not supported on a slab of a multi-GPU domain "
+                                 "(the migration payload does not carry the ids)");
+    return GSMPM_ESTATE;
+  }
+  if (h->fold) {
+    set_error(std::string(who) + ": per-particle materials are not supported by the folded pipeline (GSMPM_FOLD=1)");
+    return GSMPM_ESTATE;
+  }
+  if (!h->has_particles) {
+    set_error(std::string(who) + ": particles not set (gsmpm_mpm_set_particles resets the ids)");
+    return GSMPM_ESTATE;
+  }
+  if (!h->mat_ids) GSMPM_HIP(hipMalloc(&h->mat_ids, sizeof(float) * (size_t)h->np));
+  if (h->mixed) return GSMPM_OK;
+  if (fill) {
+    hipLaunchKernelGGL(k_fill_f, dim3(div_up(h->n, 256)), dim3(256), 0, st, h->mat_ids, h->n, (float)h->prm.material);
+    GSMPM_LAUNCH_CHECK();
+  }
+  h->mixed = true;
+  if (!h->rebin_set) {  // the material default changes: the adaptive count of the last call goes with it
+    h->rebin_interval = kRebinStress;
+    h->rebin_m = 0;
+  }
+  drop_graphs(h);
+  return GSMPM_OK;
+}
+static void leave_mixed(gsmpm_mpm* h) {
+  h->mixed = false;
+  if (!h->rebin_set) {
+    h->rebin_interval = h->mat_kernel == 0 ? kRebinStressFree : kRebinStress;
+    h->rebin_m = 0;
+  }
+  drop_graphs(h);
 }
 
 // plane of a field; *cold: a cold plane (caller order)
@@ -2650,7 +2753,7 @@ static int graph_substeps(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc, 
 extern "C" {
 
 const char* gsmpm_last_error(void) { return g_err.c_str(); }
-int gsmpm_version(void) { return 1; }
+int gsmpm_version(void) { return 2; }
 
 int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
   GSMPM_REQUIRE(prm && out, "gsmpm_mpm_create: null argument");
@@ -2872,6 +2975,7 @@ int gsmpm_mpm_destroy(gsmpm_mpm* h) {
   (void)hipFree(h->planes);
   (void)hipFree(h->cold);
   (void)hipFree(h->orig);
+  (void)hipFree(h->mat_ids);
   (void)hipFree(h->gacc);
   (void)hipFree(h->gvel);
   (void)hipFree(h->dev_bc);
@@ -2986,6 +3090,8 @@ int gsmpm_mpm_set_particles(gsmpm_mpm* h, const float* x, const float* cov6, con
   a.yield0 = (float)h->prm.yield_stress;                  // model.py:56
   hipLaunchKernelGGL(k_init, dim3(div_up(h->n, 256)), dim3(256), 0, st, particles_of(h), a);
   GSMPM_LAUNCH_CHECK();
+  // the material ids go back to the create-time material with mu / lam / yield (k_init)
+  if (h->mixed) leave_mixed(h);
   const size_t nn = (size_t)h->g.ng * h->g.ng * h->g.ng;
   GSMPM_HIP(hipMemsetAsync(h->gacc, 0, nn * sizeof(float4), st));
   GSMPM_HIP(hipMemsetAsync(h->gvel, 0, nn * sizeof(float4), st));
@@ -3152,6 +3258,7 @@ int gsmpm_mpm_set_rebin_interval(gsmpm_mpm* h, int32_t substeps) {
   GSMPM_REQUIRE(h, "gsmpm_mpm_set_rebin_interval: null handle");
   GSMPM_REQUIRE(substeps >= 1, "gsmpm_mpm_set_rebin_interval: substeps must be >= 1");
   h->rebin_interval = substeps;
+  h->rebin_set = true;
   h->rebin_auto = false;  // a fixed spacing, as asked
   h->rebin_m = 0;
   return GSMPM_OK;
@@ -3207,6 +3314,7 @@ int gsmpm_mpm_postprocess(gsmpm_mpm* h, void* stream) {
 }
 
 int gsmpm_mpm_field_width(int32_t field) {
+  if (field == GSMPM_FIELD_MATERIAL) return 1;
   int w;
   if (plane_of(field, &w) < 0) return GSMPM_EINVAL;
   return w;
@@ -3214,6 +3322,15 @@ int gsmpm_mpm_field_width(int32_t field) {
 
 int gsmpm_mpm_get(gsmpm_mpm* h, int32_t field, float* out, void* stream) {
   GSMPM_REQUIRE(h && out, "gsmpm_mpm_get: null argument");
+  if (field == GSMPM_FIELD_MATERIAL) {  // caller order as stored; a uniform handle: the create-time code
+    hipStream_t st = (hipStream_t)stream;
+    if (h->mixed)
+      GSMPM_HIP(hipMemcpyAsync(out, h->mat_ids, sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+    else
+      hipLaunchKernelGGL(k_fill_f, dim3(div_up(h->n, 256)), dim3(256), 0, st, out, h->n, (float)h->prm.material);
+    GSMPM_LAUNCH_CHECK();
+    return GSMPM_OK;
+  }
   int w, cold;
   const int p0 = plane_of(field, &w, &cold);
   GSMPM_REQUIRE(p0 >= 0, "gsmpm_mpm_get: unknown field");
@@ -3225,6 +3342,13 @@ int gsmpm_mpm_get(gsmpm_mpm* h, int32_t field, float* out, void* stream) {
 
 int gsmpm_mpm_set(gsmpm_mpm* h, int32_t field, const float* in, void* stream) {
   GSMPM_REQUIRE(h && in, "gsmpm_mpm_set: null argument");
+  if (field == GSMPM_FIELD_MATERIAL) {  // the floats as given; the handle is mixed from here on
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = enter_mixed(h, "gsmpm_mpm_set(GSMPM_FIELD_MATERIAL)", false, st);
+    if (rc) return rc;
+    GSMPM_HIP(hipMemcpyAsync(h->mat_ids, in, sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+    return GSMPM_OK;
+  }
   int w, cold;
   const int p0 = plane_of(field, &w, &cold);
   GSMPM_REQUIRE(p0 >= 0, "gsmpm_mpm_set: unknown field");
@@ -3232,6 +3356,58 @@ int gsmpm_mpm_set(gsmpm_mpm* h, int32_t field, const float* in, void* stream) {
   hipLaunchKernelGGL(k_set, dim3(div_up(h->n, 256)), dim3(256), 0, st, particles_of(h), h->orig, p0, w, cold, in);
   GSMPM_LAUNCH_CHECK();
   if (field == GSMPM_FIELD_X) return rebin(h, st);
+  return GSMPM_OK;
+}
+
+int gsmpm_mpm_material_mode(gsmpm_mpm* h) {
+  GSMPM_REQUIRE(h, "gsmpm_mpm_material_mode: null handle");
+  return h->mixed ? 1 : 0;
+}
+
+static RegionBox region_box(const double c[3], const double s[3]) {
+  RegionBox b;
+  for (int d = 0; d < 3; ++d) {
+    b.c[d] = (float)c[d];
+    b.s[d] = (float)s[d];
+  }
+  return b;
+}
+
+int gsmpm_mpm_set_region_material(gsmpm_mpm* h, const double center[3], const double size[3], int32_t material,
+                                  void* stream) {
+  GSMPM_REQUIRE(h && center && size, "gsmpm_mpm_set_region_material: null argument");
+  if (material < 0 || material > 3) {  // model.py:27-30
+    set_error("Material not supported yet");
+    return GSMPM_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = enter_mixed(h, "gsmpm_mpm_set_region_material", true, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_region_material, dim3(div_up(h->n, 256)), dim3(256), 0, st, particles_of(h),
+                     (const int*)h->orig, region_box(center, size), (float)material, h->mat_ids);
+  GSMPM_LAUNCH_CHECK();
+  return GSMPM_OK;
+}
+
+int gsmpm_mpm_set_region_params(gsmpm_mpm* h, const double center[3], const double size[3], double E, double nu,
+                                double density, double mu_override, void* stream) {
+  GSMPM_REQUIRE(h && center && size, "gsmpm_mpm_set_region_params: null argument");
+  GSMPM_REQUIRE(E > 0 && nu > 0 && nu < 0.49, "gsmpm_mpm_set_region_params: need E > 0 and 0 < nu < 0.49");
+  if (h->slab) {
+    set_error("gsmpm_mpm_set_region_params: region overrides are not supported on a slab of a multi-GPU domain");
+    return GSMPM_ESTATE;
+  }
+  if (!h->has_particles) {
+    set_error("gsmpm_mpm_set_region_params: particles not set");
+    return GSMPM_ESTATE;
+  }
+  const float logE = (float)std::log10(E);              // model.py:42, as gsmpm_mpm_set_particles
+  const float y = (float)(-std::log(0.49 / nu - 1.0));  // model.py:43
+  // boundary_conditions.py:69: mu == 1000 is the "no override" sentinel
+  hipLaunchKernelGGL(k_region_params, dim3(div_up(h->n, 256)), dim3(256), 0, (hipStream_t)stream, particles_of(h),
+                     region_box(center, size), logE, y, (float)density, mu_override != 1000.0 ? 1 : 0,
+                     (float)mu_override);
+  GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }
 
@@ -3364,11 +3540,12 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
     return GSMPM_OK;
   };
   int rc = timed(0, [&]() {
-    switch (h->mat_kernel) {
+    switch (kernel_code(h)) {
       case 0: launch_p2g<0>(h, c, bc_active, dt, st, nullptr); break;
       case 1: launch_p2g<1>(h, c, bc_active, dt, st, nullptr); break;
       case 2: launch_p2g<2>(h, c, bc_active, dt, st, nullptr); break;
       case 3: launch_p2g<3>(h, c, bc_active, dt, st, nullptr); break;
+      case kMatMixed: launch_p2g<kMatMixed>(h, c, bc_active, dt, st, nullptr); break;
       default: launch_p2g<4>(h, c, bc_active, dt, st, nullptr); break;
     }
   });
@@ -3490,6 +3667,22 @@ int gsmpm_constitutive(int32_t material, const float* Ft, int32_t n, const float
     case 4: hipLaunchKernelGGL(k_constitutive<4>, g, b, 0, st, Ft, n, mu, lam, yld, dt, mc, Fo, To); break;
     default: hipLaunchKernelGGL(k_constitutive<5>, g, b, 0, st, Ft, n, mu, lam, yld, dt, mc, Fo, To); break;
   }
+  GSMPM_LAUNCH_CHECK();
+  return GSMPM_OK;
+}
+
+int gsmpm_constitutive_mixed(const float* material, const float* Ft, int32_t n, const float* mu, const float* lam,
+                             float* yld, float dt, int32_t jelly_fcr, float* Fo, float* To, void* stream) {
+  GSMPM_REQUIRE(material && Ft && mu && lam && yld && Fo && To && n >= 0, "gsmpm_constitutive_mixed: bad argument");
+  if (n == 0) return GSMPM_OK;
+  MatConsts mc;  // gsmpm_constitutive's
+  const double sin_phi = std::sin(25.0 / 180.0 * 3.141592653589793);
+  mc.alpha = (float)(std::sqrt(2.0 / 3.0) * 2.0 * sin_phi / (3.0 - sin_phi));
+  mc.hardening = 1.0f;
+  mc.xi = 1.0f;
+  mc.pvisc = 0.008f;
+  hipLaunchKernelGGL(k_constitutive_mixed, dim3(div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, material, Ft, n, mu,
+                     lam, yld, dt, mc, jelly_fcr ? 4 : 0, Fo, To);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }

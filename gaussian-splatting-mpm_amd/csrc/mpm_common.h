@@ -90,6 +90,22 @@ struct Particles {
   __device__ __forceinline__ void stc(int plane, int row, float v) const { cold[(size_t)plane * np + row] = v; }
 };
 
+// Per-particle material ids (mixed mode, constitutive.h): the last argument
+// of the mixed P2G kernels (k_fused_mixed, k_p2g_mixed).  Empty for every
+// uniform instantiation, whose kernels do not take it; the mixed one
+// (MAT == 6) carries the id array in CALLER order, read through the storage
+// -> caller map, so a re-bin or re-sort never moves it (NPLANES stays what
+// it is).
+template <int MAT>
+struct MatIds {};
+template <>
+struct MatIds<6> {
+  const float* mat;  // [n] the reference's model.material, caller order
+  const int* orig;   // [n] caller row of each storage row
+  int jelly;         // kernel code of the `else` rows: 0 as written, 4 FCR
+  __device__ __forceinline__ float id(int p) const { return mat[orig[p]]; }
+};
+
 struct GridDims {
   int ng;
   float dx, inv_dx;

@@ -625,6 +625,11 @@ int gsmpm_rccl_comm_destroy(void* comm) {
 int gsmpm_mpm_slab_init(gsmpm_mpm* h, int32_t rank, int32_t world, int32_t lo, int32_t hi, int32_t margin,
                         int32_t interval) {
   GSMPM_REQUIRE(h, "gsmpm_mpm_slab_init: null handle");
+  if (h->mixed) {
+    set_error("gsmpm_mpm_slab_init: the handle holds per-particle materials, which slabs do not support "
+              "(the migration payload does not carry the ids)");
+    return GSMPM_ESTATE;
+  }
   GSMPM_REQUIRE(h->fused, "gsmpm_mpm_slab_init: slabs run the fused pipeline (no GSMPM_FLAG_PHASED / KEEP_GRID)");
   GSMPM_REQUIRE(!h->has_particles, "gsmpm_mpm_slab_init: call before setting particles");
   GSMPM_REQUIRE(!h->slab, "gsmpm_mpm_slab_init: already a slab");

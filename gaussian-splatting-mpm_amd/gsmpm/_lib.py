@@ -107,6 +107,12 @@ _SIGS = {
     "gsmpm_mpm_field_width": (ctypes.c_int, [ctypes.c_int32]),
     "gsmpm_mpm_get": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
     "gsmpm_mpm_set": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
+    "gsmpm_mpm_material_mode": (ctypes.c_int, [c_void_p]),
+    "gsmpm_mpm_set_region_material": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
+                                                      ctypes.c_int32, c_void_p]),
+    "gsmpm_mpm_set_region_params": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
+                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double, c_void_p]),
     "gsmpm_mpm_get_grid": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
     "gsmpm_mpm_world_outputs": (ctypes.c_int, [c_void_p, ctypes.c_float, ctypes.c_float * 3, ctypes.c_int32,
                                                c_void_p, c_void_p, c_void_p]),
@@ -121,6 +127,8 @@ _SIGS = {
     "gsmpm_svd3": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsmpm_constitutive": (ctypes.c_int, [ctypes.c_int32, c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_void_p,
                                           ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "gsmpm_constitutive_mixed": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_void_p,
+                                                ctypes.c_float, ctypes.c_int32, c_void_p, c_void_p, c_void_p]),
     "gsmpm_particle_volume": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_void_p,
                                              c_void_p, c_void_p]),
     "gsmpm_fit_create": (ctypes.c_int, [ctypes.POINTER(FitParams), ctypes.POINTER(c_void_p)]),
@@ -178,7 +186,7 @@ class Transport(ctypes.Structure):
 
 # field ids (include/gsmpm.h)
 FIELD = {"x": 0, "v": 1, "C": 2, "F_trial": 3, "cov": 4, "init_cov": 5, "R": 6, "mass": 7, "vol": 8, "mu": 9,
-         "lam": 10, "yield_stress": 11}
+         "lam": 10, "yield_stress": 11, "material": 12}
 FIT_FIELD = {k: i for i, k in enumerate(
     ("x", "v", "F", "C", "stress", "gx", "gv", "gF", "gC", "gstress", "logE", "y", "mu", "lam", "glogE", "gy", "gmu",
      "glam", "cov", "gcov", "init_cov", "vol", "mass"))}

@@ -16,7 +16,7 @@ from ._lib import LIB, check, ptr, stream_of
 MATERIALS = {"jelly": 0, "metal": 1, "sand": 2, "foam": 3}  # mpm_solver/utils.py:5-10
 
 _WIDTH = {"x": 3, "v": 3, "C": 9, "F_trial": 9, "cov": 6, "init_cov": 6, "R": 9, "mass": 1, "vol": 1, "mu": 1,
-          "lam": 1, "yield_stress": 1}
+          "lam": 1, "yield_stress": 1, "material": 1}
 
 
 def _d3(v):
@@ -85,6 +85,31 @@ class Simulator:
     def add_plane_collider(self, point, normal, friction=0.0) -> int:
         return check(LIB.gsmpm_mpm_add_plane_collider(self._h, _d3(point), _d3(normal), float(friction)),
                      "add_plane_collider")
+
+    # ------------------------------------------------ per-particle materials --
+    @property
+    def material_mode(self) -> int:
+        """0: one material (chosen at create); 1: mixed -- each particle's stress
+        follows its own ``material`` value (gsmpm_mpm_material_mode).  Entered by
+        ``set("material", t)`` or ``set_region_material``; lasts until
+        ``set_particles``."""
+        return check(LIB.gsmpm_mpm_material_mode(self._h), "gsmpm_mpm_material_mode")
+
+    def set_region_material(self, center, size, material):
+        """modify_material (boundary_conditions.py:74-85): the particles now
+        inside the box |x - center| < size get `material` (a name or a code)."""
+        code = MATERIALS.get(material, -1) if isinstance(material, str) else int(material)
+        if code not in (0, 1, 2, 3):
+            raise TypeError("Material not supported yet")  # model.py:27-30
+        check(LIB.gsmpm_mpm_set_region_material(self._h, _d3(center), _d3(size), code, stream_of(self.device)),
+              "gsmpm_mpm_set_region_material")
+
+    def set_region_params(self, center, size, E, nu, density, mu=1000):
+        """additional_params (boundary_conditions.py:47-70): the particles now
+        inside the box get mu / lam from E and nu, mass = density * vol, and
+        mu = `mu` unless it is the reference's sentinel 1000."""
+        check(LIB.gsmpm_mpm_set_region_params(self._h, _d3(center), _d3(size), float(E), float(nu), float(density),
+                                              float(mu), stream_of(self.device)), "gsmpm_mpm_set_region_params")
 
     # ------------------------------------------------------------ stepping --
     def step(self, dt: float, masks):

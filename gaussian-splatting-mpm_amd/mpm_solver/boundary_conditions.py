@@ -2,9 +2,13 @@
 
 Same constructor arguments, attributes, ``isActive`` windows and type
 registries as the reference; the per-node / per-particle work runs inside the
-fused HIP kernels (fixed cubes in k_grid, impulses in k_p2g).
+fused HIP kernels (fixed cubes in k_grid, impulses in k_p2g).  The two
+region records (additional_params, modify_material) are applied once, when
+``set_boundary_conditions`` ends, through the library's region calls.
 """
 from __future__ import annotations
+
+from mpm_solver.utils import material_types
 
 
 class BasicBC:
@@ -40,7 +44,11 @@ class MaterialParamsModifier(BasicBC):
 
     In the reference its apply() writes ``model.nu[p]`` / ``model.E[p]``,
     fields MPM_model never defines, so any config using it raises
-    AttributeError.  Kept as an error here too.
+    AttributeError before the record takes effect.  Here the
+    record does what it plainly means: the particles inside the box get mu /
+    lam from E and nu, mass from density, and ``applymu`` replaces mu unless
+    it is the sentinel 1000 (gsmpm_mpm_set_region_params does all three).
+    The fitting path only collects the record.
     """
 
     def __init__(self, n_particles, bc_args, sim_args):
@@ -52,22 +60,60 @@ class MaterialParamsModifier(BasicBC):
         super().__init__(n_particles, bc_args, sim_args)
 
     def apply(self, state, model):
-        raise AttributeError("'MPM_model' object has no attribute 'nu' "
-                             "(additional_params is broken in the reference, SURVEY F9)")
+        sim = _forward_sim(model, "additional_params")
+        model._owner.flush()
+        state._override_density(self.center, self.size, self.density)  # particle_density[p] = density (:63)
+        sim.set_region_params(self.center, self.size, self.E, self.nu, self.density, self.mu)
+
+    def applymu(self, state, model):
+        """boundary_conditions.py:65-70 alone: mu inside the box, unless 1000.
+        Kept for the reference's API shape only: apply() already took the
+        override with E, nu and density in one region call, and
+        set_boundary_conditions never calls this.  Called on its own it sets
+        mu through the field views (a get and a set), not a kernel."""
+        if self.mu == 1000:
+            return
+        sim = _forward_sim(model, "additional_params")
+        model._owner.flush()
+        import torch
+        x = sim.get("x")
+        c = torch.tensor(self.center, dtype=torch.float32, device=x.device)
+        sz = torch.tensor(self.size, dtype=torch.float32, device=x.device)
+        mu = sim.get("mu")
+        mu[((x - c).abs() < sz).all(dim=1)] = float(self.mu)
+        sim.set("mu", mu)
 
 
 class MaterialTypeModifier(BasicBC):
-    """modify_material (boundary_conditions.py:74-85): writes a string into the f32
-    material field in the reference, which Taichi rejects."""
+    """modify_material (boundary_conditions.py:74-85): the particles inside the
+    box take another material.  ``material`` is an int code, as the reference's
+    configs give it, or a name from ``material_types``; an unknown name raises
+    the reference's "Material not supported yet" TypeError (model.py:27-30).
+    The simulator enters mixed mode (gsmpm_mpm_set_region_material)."""
 
     def __init__(self, n_particles, bc_args, sim_args):
         self.material = bc_args["material"]
+        if isinstance(self.material, str):
+            if self.material not in material_types:
+                raise TypeError("Material not supported yet")
+            self.material_code = material_types[self.material]
+        else:
+            self.material_code = int(self.material)
         self.isMaterial = True
         super().__init__(n_particles, bc_args, sim_args)
 
     def apply(self, state, model):
-        raise TypeError("modify_material assigns a string to the f32 material field "
-                        "(broken in the reference, SURVEY F9)")
+        sim = _forward_sim(model, "modify_material")
+        model._owner.flush()
+        sim.set_region_material(self.center, self.size, self.material_code)
+
+
+def _forward_sim(model, what):
+    owner = getattr(model, "_owner", None)
+    sim = getattr(owner, "_sim", None)
+    if sim is None:
+        raise AttributeError(f"{what} applies to the forward-only simulator (the fitting path only collects it)")
+    return sim
 
 
 class StickyGroundBC(BasicBC):

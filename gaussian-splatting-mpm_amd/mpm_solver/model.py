@@ -78,7 +78,8 @@ class MPM_model:
         sim = owner._sim
         n = self.n_particles
         dev = sim.device
-        self.material = FieldView(owner, lambda: torch.full((n,), float(self.material_code), device=dev), shape=(n,))
+        # model.material (model.py:24-31): per particle; writing it puts the simulator in mixed mode
+        self.material = FieldView(owner, lambda: sim.get("material"), lambda t: sim.set("material", t), shape=(n,))
         self.logE = FieldView(owner, lambda: torch.full((n,), self._logE, dtype=torch.float32, device=dev), shape=(n,))
         self.y = FieldView(owner, lambda: torch.full((n,), self._y, dtype=torch.float32, device=dev), shape=(n,))
         self.mu = FieldView(owner, lambda: sim.get("mu"), lambda t: sim.set("mu", t), shape=(n,))
@@ -181,6 +182,7 @@ class MPM_state:
         self.n_particles = n
         dev = sim.device
         density = float(args.density)
+        self.args_density = density
         self.particle_xyz = FieldView(owner, lambda: sim.get("x"), lambda t: sim.set("x", t.reshape(-1, 3)), (n, 3))
         self.particle_vel = FieldView(owner, lambda: sim.get("v"), lambda t: sim.set("v", t.reshape(-1, 3)), (n, 3))
         self.particle_C = FieldView(owner, lambda: sim.get("C").view(n, 3, 3), lambda t: sim.set("C", t), (n, 3, 3))
@@ -191,10 +193,25 @@ class MPM_state:
         self.particle_R = FieldView(owner, lambda: sim.get("R").view(n, 3, 3), None, (n, 3, 3))
         self.particle_mass = FieldView(owner, lambda: sim.get("mass"), None, (n,))
         self.particle_vol = FieldView(owner, lambda: sim.get("vol"), None, (n,))
-        self.particle_density = FieldView(owner, lambda: torch.full((n,), density, device=dev), None, (n,))
+        # the plain fill (model.py:100-102) until an additional_params record overrides a region
+        self._sim = sim
+        self._density = None
+        self.particle_density = FieldView(
+            owner, lambda: torch.full((n,), density, device=dev) if self._density is None else self._density.clone(),
+            None, (n,))
         self.grid_mass = FieldView(owner, lambda: sim.get_grid("mass"), None, (ng, ng, ng))
         self.grid_v_in = FieldView(owner, lambda: sim.get_grid("v_in"), None, (ng, ng, ng, 3))
         self.grid_v_out = FieldView(owner, lambda: sim.get_grid("v_out"), None, (ng, ng, ng, 3))
+
+    def _override_density(self, center, size, density):
+        """particle_density inside the box |x - center| < size (the region records'
+        f32 test on the current positions, boundary_conditions.py:60-63)."""
+        x = self._sim.get("x")
+        if self._density is None:
+            self._density = torch.full((self.n_particles,), float(self.args_density), device=x.device)
+        c = torch.tensor([float(v) for v in center], dtype=torch.float32, device=x.device)
+        s = torch.tensor([float(v) for v in size], dtype=torch.float32, device=x.device)
+        self._density[((x - c).abs() < s).all(dim=1)] = float(density)
 
     @property
     def particle_F(self):

@@ -123,6 +123,9 @@ class MPM_Simulator:
                 self.grid_postprocess.append(bc)
             if bc.type in init_bc:
                 self.init_particles.append(bc)
+        # solver.py:125-129, in list order (a later box overrides an earlier one).  An
+        # additional_params record's apply() covers the reference's three steps
+        # (apply, compute_mu_lam_from_E_nu, applymu) in one region call.
         for pp in self.init_particles:
             pp.apply(self.mpm_state, self.mpm_model)
 

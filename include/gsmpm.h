@@ -262,10 +262,61 @@ int gsmpm_mpm_postprocess(gsmpm_mpm* h, void* stream);
 #define GSMPM_FIELD_MU 9       /* mpm_model.mu      [N]     */
 #define GSMPM_FIELD_LAM 10     /* mpm_model.lam     [N]     */
 #define GSMPM_FIELD_YIELD 11   /* mpm_model.yield_stress [N] */
-#define GSMPM_FIELD_COUNT 12
+#define GSMPM_FIELD_MATERIAL 12 /* mpm_model.material [N]  (per-particle materials, below) */
+#define GSMPM_FIELD_COUNT 13
 int gsmpm_mpm_field_width(int32_t field);
 int gsmpm_mpm_get(gsmpm_mpm* h, int32_t field, float* out, void* stream);
 int gsmpm_mpm_set(gsmpm_mpm* h, int32_t field, const float* in, void* stream);
+
+/* Per-particle materials (the reference's f32 model.material, dispatched per
+ * particle by compute_stress_from_F_trial, utils.py:13-54).  A handle is
+ * uniform (one material, chosen at create) until it enters MIXED mode:
+ *   - gsmpm_mpm_set(GSMPM_FIELD_MATERIAL) stores the floats as given (caller
+ *     order) and enters mixed mode; no host sync, no check that they differ;
+ *   - gsmpm_mpm_set_region_material enters it too.
+ * In mixed mode the stress of each particle follows its own value as the
+ * reference's comparisons read it: == 1 metal, == 2 sand, == 3 foam; anything
+ * else (0, other numbers, NaN) is the `else` branch, F = F_trial with the
+ * jelly rule of the handle (zero stress as written, SURVEY F3, or FCR when
+ * created with GSMPM_FLAG_JELLY_FCR).  The re-binning interval takes the
+ * stress-bearing default unless the caller set one.  gsmpm_mpm_get works on
+ * any handle; a uniform one returns the create-time code in every row.
+ * On a mixed handle metal rows run the reference's own SVD sequence
+ * (correctly rounded square roots, a second SVD of the returned F for the
+ * stress) where a uniform metal handle runs a refined-rsqrt SVD and reuses its
+ * factors: a scene salted particle by particle needs it to stay within the
+ * parity bounds.  So a metal particle's results differ in the last bits
+ * between a mixed and a uniform handle, and the mixed kernel costs more
+ * (k_fused, lego 100k, every id metal: 33.9 us against 22.8 us a launch).
+ * Mixed mode lasts until gsmpm_mpm_set_particles, which resets the ids to the
+ * create-time material as it re-initialises mu / lam / yield.
+ * Not supported (GSMPM_ESTATE, nothing launched, the message says why): a
+ * slab handle, GSMPM_FOLD=1, and gsmpm_mpm_slab_init on a mixed handle.  The
+ * differentiable simulator (gsmpm_fit_*) has one material. */
+/* 0 uniform, 1 mixed */
+int gsmpm_mpm_material_mode(gsmpm_mpm* h);
+/* The region records of boundary_conditions.py:47-85 as their plain intent
+ * (the reference raises before either takes effect).  Both run the
+ * impulse's box test, fabsf(x - center) < size on all three axes, strict, in
+ * f32, on the particles' current positions; asynchronous on `stream`; applied
+ * in call order, so a later box overrides an earlier one.
+ * set_region_material (modify_material): rows inside get `material`
+ *   (GSMPM_MAT_*, else GSMPM_EINVAL); enters mixed mode.
+ * set_region_params (additional_params): rows inside get mu and lam from E
+ *   and nu by the path create takes (model.py:41-44, utils.py:349-362: the
+ *   create-time E and nu reproduce the create-time mu / lam bit for bit),
+ *   mass = f32(density) * vol, and then mu = mu_override unless that is
+ *   exactly 1000, the reference's sentinel (boundary_conditions.py:69).  Does
+ *   not by itself enter mixed mode.  Needs E > 0 and 0 < nu < 0.49 (the
+ *   logit of nu the create path takes, else GSMPM_EINVAL) and particles set;
+ *   refused on a slab handle (GSMPM_ESTATE: the positions and planes there
+ *   are one rank's share, and the box would have to be applied on every rank
+ *   before the first migration).
+ * Both need gsmpm_mpm_set_particles first (GSMPM_ESTATE otherwise). */
+int gsmpm_mpm_set_region_material(gsmpm_mpm* h, const double center[3], const double size[3], int32_t material,
+                                  void* stream);
+int gsmpm_mpm_set_region_params(gsmpm_mpm* h, const double center[3], const double size[3], double E, double nu,
+                                double density, double mu_override, void* stream);
 
 /* Grid readback [n^3] / [n^3,3] (grid_mass / grid_v_in / grid_v_out,
  * model.py:117-121).  mass and v_in need GSMPM_FLAG_KEEP_GRID. */
@@ -320,6 +371,12 @@ int gsmpm_svd3(const float* A, int32_t n, float* U, float* sig, float* V, void* 
  * never dispatched by the reference) with StVK stress.  Test entry point. */
 int gsmpm_constitutive(int32_t material, const float* F_trial, int32_t n, const float* mu, const float* lam,
                        float* yield, float dt, float* F_out, float* tau_out, void* stream);
+/* The same with a material value per row (material[n], read as mixed mode
+ * reads it); jelly_fcr != 0: the `else` rows take FCR.  yield is written for
+ * metal rows only.  Test entry point of the mixed dispatch. */
+int gsmpm_constitutive_mixed(const float* material, const float* F_trial, int32_t n, const float* mu,
+                             const float* lam, float* yield, float dt, int32_t jelly_fcr, float* F_out,
+                             float* tau_out, void* stream);
 
 /* get_particle_volume (internel_filling/filling.py:27-42): vol[N] from
  * x[N,3] (grid space) with an n^3 i32 count grid in `scratch` (>= 4*n^3 B). */
