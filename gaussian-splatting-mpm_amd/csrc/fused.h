@@ -22,8 +22,9 @@
 // tiles of 8 x 8 x 7 cells that is 12 x 12 x 11 = 1584 nodes, 50.7 KB of u64
 // accumulators -- three workgroups per CU.  A particle that moved further
 // gathers from the dense v_out and scatters with global float atomics into
-// the dense accumulator, and raises the escape flag that makes the next grid
-// update sweep every tile (correct for any motion, fast for CFL-bounded
+// the dense accumulator, raises the escape flag and appends the tiles that own
+// its stencil nodes to the touched list, so the next grid update adds the
+// accumulator to those nodes (correct for any motion, fast for CFL-bounded
 // motion; the lego scene moves < 0.06 cells per substep).
 //
 // Binning is done by the G2P half of k_fused every `rebin_interval` substeps
@@ -38,31 +39,8 @@ constexpr int kFW0 = kFT0 + 4, kFW1 = kFT1 + 4, kFW2 = kFT2 + 4;  // window node
 constexpr int kFWin = kFW0 * kFW1 * kFW2;                      // 1584
 constexpr int kFTN = kFT0 * kFT1 * kFT2;                       // owned nodes per tile (448)
 
-// Where window node (w0, w1, w2) lives in its chunk's slot.  Default: window
-// order ([kFW0][kFW1][kFW2]).  GSMPM_OWNER_SLOTS=1 (A/B): grouped by the tile
-// that owns the node -- per axis the window's coords split into sections
-// w = 0 (the lower neighbour's last plane), 1..T (the tile's own), T+1..T+3
-// (the upper neighbour's first three), and the 27 section boxes are stored
-// one after another, each in its owner tile's node order.  A grid-update wave
-// (64 consecutive owned nodes of one tile) then reads the own tile's box and
-// the lower-x neighbour's as one contiguous 1 KB run instead of 9 runs of 7
-// nodes 11 apart.
-#ifndef GSMPM_OWNER_SLOTS
-#define GSMPM_OWNER_SLOTS 0
-#endif
-constexpr bool kOwnerSlots = GSMPM_OWNER_SLOTS != 0;
-__device__ __forceinline__ int slot_sec_pre(int w, int T) { return w == 0 ? 0 : (w <= T ? 1 : T + 1); }
-__device__ __forceinline__ int slot_sec_n(int w, int T) { return w == 0 ? 1 : (w <= T ? T : 3); }
-__device__ __forceinline__ int slot_loc(int w0, int w1, int w2) {
-  if constexpr (!kOwnerSlots) {
-    return (w0 * kFW1 + w1) * kFW2 + w2;
-  } else {
-    const int p0 = slot_sec_pre(w0, kFT0), n0 = slot_sec_n(w0, kFT0);
-    const int p1 = slot_sec_pre(w1, kFT1), n1 = slot_sec_n(w1, kFT1);
-    const int p2 = slot_sec_pre(w2, kFT2), n2 = slot_sec_n(w2, kFT2);
-    return p0 * (kFW1 * kFW2) + n0 * (p1 * kFW2 + n1 * p2) + ((w0 - p0) * n1 + (w1 - p1)) * n2 + (w2 - p2);
-  }
-}
+// where window node (w0, w1, w2) lives in its chunk's slot: window order ([kFW0][kFW1][kFW2])
+__device__ __forceinline__ int slot_loc(int w0, int w1, int w2) { return (w0 * kFW1 + w1) * kFW2 + w2; }
 
 // ---- multi-GPU slab hooks (slab.h has the exchange and migration kernels) ----
 struct SlabWin {
@@ -450,13 +428,9 @@ __device__ __forceinline__ void base_of(const float (&x)[3], float inv_dx, int (
 // outside the grid) adds the tiles owning its in-grid stencil nodes to the
 // touched list, as add_lower_tiles does for a new lower neighbour, so the
 // next k_grid_f -- which adds the accumulator to the nodes it owns and zeroes
-// it -- finds every node an escape wrote among the touched tiles.  Round 5
-// swept every tile of the grid after any escape (4,864 tiles at 128^3 against
-// ~900 touched); GSMPM_ESC_SWEEP=1 restores that (A/B).
-#ifndef GSMPM_ESC_SWEEP
-#define GSMPM_ESC_SWEEP 0
-#endif
-constexpr bool kEscSweepAll = GSMPM_ESC_SWEEP != 0;
+// it -- finds every node an escape wrote among the touched tiles (round 5
+// swept every tile of the grid after any escape: 4,864 tiles at 128^3 against
+// ~900 touched).
 __device__ __forceinline__ void mark_escape_tiles(int* __restrict__ tflag, int* __restrict__ touched,
                                                int* __restrict__ ntouch, int2* __restrict__ rcov, const FTiles& tl,
                                                int ng, int b0, int b1, int b2) {
@@ -498,27 +472,6 @@ __device__ __forceinline__ bool in_grid(const float (&x)[3], const GridDims& g) 
 #ifndef GSMPM_STORE_VC
 #define GSMPM_STORE_VC 0  // 1: every G2P stores v and C (A/B)
 #endif
-// GSMPM_ZERO_BOX=1: the P2G half zeroes only its chunk's store box of the LDS
-// window (the nodes its stencils reach: ~57 % of the 1,584 on the lego
-// frame), once the box is known, with one more workgroup barrier, instead
-// of the whole window before it.  Measured and rejected (round 4, 2 A/B
-// rounds on the lego bench, profiles/r04/ab_libs_r04e.txt): sim 3.120 / 3.129
-// against 3.115 / 3.100 ms/frame, k_fused 17.0 against 16.9 us -- the zeroing
-// is hidden under the particle loads it overlaps; the barrier is not
-#ifndef GSMPM_ZERO_BOX
-#define GSMPM_ZERO_BOX 0
-#endif
-constexpr bool kZeroBox = GSMPM_ZERO_BOX != 0;
-// GSMPM_ATOMIC_GRID=1: the P2G half adds its window box into the dense
-// accumulator gacc with global float atomics (one lane per node channel)
-// instead of storing it to the chunk's slot, and k_grid_f reads one node of
-// gacc (and zeroes it) instead of summing <= 8 covering slots through the
-// 27-tile cover table.  The cross-chunk sum becomes order-dependent f32 (as
-// the reference's Taichi atomics are); within a chunk it stays exact (A/B)
-#ifndef GSMPM_ATOMIC_GRID
-#define GSMPM_ATOMIC_GRID 0
-#endif
-constexpr bool kAtomicGrid = GSMPM_ATOMIC_GRID != 0;
 // GSMPM_SIM_PRIO=n (A/B): the simulator's waves raise their issue priority
 // (s_setprio n, 0..3) so that a SIMD's arbiter serves them before the waves of
 // the render of the previous frame, which runs on a second stream beside them
@@ -737,7 +690,7 @@ __device__ __forceinline__ void node_extra(const float4* __restrict__ slots, con
 // 12.45, four 112-lane 12.1, seven 64-lane 12.2 with k_fused unaffected
 // (sim 3.27-3.28 against 3.29-3.32 ms/frame for two).
 // esc_in: some particle scattered through gacc in the P2G this update consumes
-// -> every tile, plus gacc (re-zeroed).  esc_clear: the flag the next P2G
+// -> gacc is added to the owned nodes (and re-zeroed).  esc_clear: the flag the next P2G
 // raises.  zc / zf (optional): the counts / touched flags the next binning
 // launch accumulates into.
 #ifndef GSMPM_GRID_PARTS
@@ -835,7 +788,7 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   const int* cnt_p = ck.nchunk;
   const int* tch_p = ck.touched;
   asm volatile("" : "+s"(esc_p), "+s"(cnt_p), "+s"(tch_p));
-  const bool recs = ck.rcov != nullptr && !kAtomicGrid;
+  const bool pre = ck.rcov != nullptr;  // workgroup-uniform: records in LDS, the next one prefetched
   const int le = threadIdx.x;  // lane: record entry
   // Cover records reach LDS by LDS-DMA (global_load_lds: no VGPR holds
   // them): buffer b of s_rec / s_box holds the tile being updated, and at the
@@ -849,7 +802,7 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   __shared__ int s_box[2][64];
   __shared__ int s_tn[2];
   // (wave 0's lanes only: the DMA writes lds_base + 4 x lane-in-wave)
-  if (recs && threadIdx.x < 64) {
+  if (pre && threadIdx.x < 64) {
     glds4(reinterpret_cast<const int*>(ck.rcov) + (size_t)i0 * 2 * kRecStride + le, &s_rec[0][0]);
     glds4(ck.rbox + (size_t)i0 * kRecStride + (le & 31), &s_box[0][0]);
   }
@@ -860,73 +813,61 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   const int T0 = __builtin_amdgcn_readfirstlane(((gint_p)tch_p)[i0]);
   const int ng = g.ng;
   const bool esc = esc0 != 0;            // the escape accumulator holds sums: add it to the owned nodes
-  const bool all = esc && kEscSweepAll;  // (A/B) every tile, not the touched ones
-  const int ntouch = all ? tl.ntiles : cnt0;  // tiles to update
-  const bool pre = recs && !all;  // workgroup-uniform: records in LDS, the next one prefetched
+  const int ntouch = cnt0;               // tiles to update
   int b = 0;
   for (int it = 0;; ++it, b ^= 1) {
     int P, part;
     grid_work(blockIdx.x, it, gridDim.x, P, part);
     if (P >= ntouch) break;  // workgroup-uniform
-    if constexpr (!kAtomicGrid) {
-      // this tile's DMA (issued a tile ago, or in the prologue) has landed;
-      // readers of the other buffer are done.  The wait is explicit: the
-      // compiler's own waits for LDS-DMA did not cover every read of these
-      // arrays (the slab test caught stale records), and a one-wave
-      // workgroup's barrier compiles to nothing.  What else it waits for is
-      // the previous tile's v_out stores (L2 write acks, not an HBM trip).
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int pn, partn;
-      grid_work(blockIdx.x, it + 1, gridDim.x, pn, partn);
-      if (pre && pn < ntouch && threadIdx.x < 64) {  // workgroup-uniform (kGridT = 64: one wave)
-        glds4(reinterpret_cast<const int*>(ck.rcov) + (size_t)pn * 2 * kRecStride + le, &s_rec[b ^ 1][0]);
-        glds4(ck.rbox + (size_t)pn * kRecStride + (le & 31), &s_box[b ^ 1][0]);
-        if (le == 0) glds4(ck.touched + pn, &s_tn[b ^ 1]);
-      }
+    // this tile's DMA (issued a tile ago, or in the prologue) has landed;
+    // readers of the other buffer are done.  The wait is explicit: the
+    // compiler's own waits for LDS-DMA did not cover every read of these
+    // arrays (the slab test caught stale records), and a one-wave
+    // workgroup's barrier compiles to nothing.  What else it waits for is
+    // the previous tile's v_out stores (L2 write acks, not an HBM trip).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    int pn, partn;
+    grid_work(blockIdx.x, it + 1, gridDim.x, pn, partn);
+    if (pre && pn < ntouch && threadIdx.x < 64) {  // workgroup-uniform (kGridT = 64: one wave)
+      glds4(reinterpret_cast<const int*>(ck.rcov) + (size_t)pn * 2 * kRecStride + le, &s_rec[b ^ 1][0]);
+      glds4(ck.rbox + (size_t)pn * kRecStride + (le & 31), &s_box[b ^ 1][0]);
+      if (le == 0) glds4(ck.touched + pn, &s_tn[b ^ 1]);
     }
     int* s_cov = s_rec[b];
     int* s_bx = s_box[b];
     const int q = threadIdx.x + part * kGridT;
     const int l0 = q / (kFT1 * kFT2), l1 = (q / kFT2) % kFT1, l2 = q % kFT2;
-    const int T = all ? P : it == 0 ? T0 : pre ? s_tn[b] : ck.touched[P];
+    const int T = it == 0 ? T0 : pre ? s_tn[b] : ck.touched[P];
     if ((unsigned)T >= (unsigned)tl.ntiles) continue;  // workgroup-uniform; never taken (P < count)
     int ti, tj, tk;
     ftile_decode(tl, T, ti, tj, tk);
     if (SLAB && pass != 0 && slab_tile_in_window(sw, ti) != (pass == 1)) continue;  // workgroup-uniform
-    if constexpr (!kAtomicGrid) {
-      if (it == 0) stamp(3, 2);
-      // a tile k_fused appended (add_lower_tiles) has no record: "none" flag
-      const bool tables = !pre || s_cov[54] != 0;  // workgroup-uniform
-      if (tables) {
-        load_cover27(ck, tbox, tl, ti, tj, tk, s_cov, s_bx);
-        __syncthreads();
-      }
+    if (it == 0) stamp(3, 2);
+    // a tile k_fused appended (add_lower_tiles) has no record: "none" flag
+    const bool tables = !pre || s_cov[54] != 0;  // workgroup-uniform
+    if (tables) {
+      load_cover27(ck, tbox, tl, ti, tj, tk, s_cov, s_bx);
+      __syncthreads();
     }
     if (it == 0) stamp(3, 3);
     const int i = ti * kFT0 + l0, j = tj * kFT1 + l1, k = tk * kFT2 + l2;
     if ((unsigned)i < (unsigned)ng && (unsigned)j < (unsigned)ng && (unsigned)k < (unsigned)ng) {
       const size_t idx = ((size_t)i * ng + j) * ng + k;
       float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-      bool reach = true;  // some stencil box covers the node (the atomic A/B form: mass only)
-      if constexpr (kAtomicGrid) {  // the node's whole sum, added by the chunks' atomics
-        a = gacc[idx];
-        if (a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f) gacc[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        NodeReads r;
-        node_reads(tl.max_chunks, s_cov, s_bx, l0, l1, l2, r);
-        reach = r.live != 0;
-        float4 v[8];
+      NodeReads r;
+      node_reads(tl.max_chunks, s_cov, s_bx, l0, l1, l2, r);
+      const bool reach = r.live != 0;  // some stencil box covers the node
+      float4 v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = ld_slot(slots, r.off[e]);
+      for (int e = 0; e < 8; ++e) v[e] = ld_slot(slots, r.off[e]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) add4(a, v[e]);
-        if (r.extra) node_extra(slots, s_cov, l0, l1, l2, r.extra, tl.max_chunks * kFWin, a);
-        if (esc) {  // the nodes an escape wrote lie in touched tiles (mark_escape_tiles); zero what was written
-          const float4 e = gacc[idx];
-          add4(a, e);
-          if (all || e.x != 0.f || e.y != 0.f || e.z != 0.f || e.w != 0.f) gacc[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+      for (int e = 0; e < 8; ++e) add4(a, v[e]);
+      if (r.extra) node_extra(slots, s_cov, l0, l1, l2, r.extra, tl.max_chunks * kFWin, a);
+      if (esc) {  // the nodes an escape wrote lie in touched tiles (mark_escape_tiles); zero what was written
+        const float4 e = gacc[idx];
+        add4(a, e);
+        if (e.x != 0.f || e.y != 0.f || e.z != 0.f || e.w != 0.f) gacc[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
       bool inrect = false;
       if constexpr (SLAB) {
@@ -938,7 +879,7 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
           sw.part[sww][((size_t)(i - sw.a[sww]) * sw.ny[sww] + (j - sw.y0[sww])) * sw.nz[sww] + (k - sw.z0[sww])] = a;
       }
       if (inrect) {
-      } else if (!kGridSkip0 || a.w != 0.f || (reach && !kAtomicGrid && GSMPM_GRID_SKIP0 == 1)) {
+      } else if (!kGridSkip0 || a.w != 0.f || (reach && GSMPM_GRID_SKIP0 == 1)) {
         if constexpr (kGvelStore == 1)
           nt_store4(gvel + idx, node_update(a, i, j, k, g, gs, bct));
         else if constexpr (kGvelStore == 2)

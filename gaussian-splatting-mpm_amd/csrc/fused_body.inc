@@ -359,7 +359,7 @@
       if (w == (int)blockIdx.x) stamp(SK, 3);
     }
     if constexpr (P2G) {
-      if (!outside && !kZeroBox) {  // 16-byte stores: half the LDS write instructions of u64 ones
+      if (!outside) {  // 16-byte stores: half the LDS write instructions of u64 ones
         uint4* z = reinterpret_cast<uint4*>(s_acc);
         for (int e = k; e < kFWin * 2; e += 256) z[e] = make_uint4(0u, 0u, 0u, 0u);
       }
@@ -458,7 +458,7 @@
           p2g_global<MAT>(x, v, C, m, nvt, g, dt, rare->gacc);
           int bq[3];
           base_of(x, g.inv_dx, bq);
-          if (!kEscSweepAll) mark_escape_tiles(rare->tflag, rare->touched, rare->nchunk + 1, rare->rcov, tl, ng, bq[0], bq[1], bq[2]);
+          mark_escape_tiles(rare->tflag, rare->touched, rare->nchunk + 1, rare->rcov, tl, ng, bq[0], bq[1], bq[2]);
         }
         if (k == 0 && cnt > 0) {
           *rare->esc = 1;
@@ -530,21 +530,6 @@
       }
       if (tpos_e >= 0) rare->rbox[(size_t)tpos_e * kRecStride + k] = (cr.w & 8) ? kFullBox : box;
       if (cr.w & 8) box = kFullBox;
-      if constexpr (kZeroBox) {  // only the nodes the scatter can reach and the store reads
-        int lo[3], hi[3];
-        box_unpack(box, lo, hi);
-        const int n1 = hi[1] - lo[1] + 1, n2 = hi[2] - lo[2] + 1, n12 = n1 * n2;
-        const int nvol = (hi[0] - lo[0] + 1) * n12;
-        const float r12 = 1.0f / (float)n12, r2 = 1.0f / (float)n2;
-        for (int qn = k; qn < nvol; qn += 256) {
-          const int a = (int)(((float)qn + 0.5f) * r12), rem = qn - a * n12;
-          const int bq = (int)(((float)rem + 0.5f) * r2), c = rem - bq * n2;
-          const int node = ((lo[0] + a) * kFW1 + lo[1] + bq) * kFW2 + lo[2] + c;
-#pragma unroll
-          for (int ch = 0; ch < 4; ++ch) s_acc[ch * kFWin + node] = 0ull;
-        }
-        __syncthreads();  // zeroing before the adds
-      }
       int ebits;
       frexpf(bmax, &ebits);
       const int S = bmax > 0.f ? 50 - ebits : 0;  // see k_p2g
@@ -565,54 +550,34 @@
         if (eb) {  // wave-uniform; rare.  (The tiles are marked here, after the scatter, not in its branch:
                    // there the code cost k_fused<metal> 1 % with no escape, profiles/r06/ab_esc_r06o.txt)
           if ((k & 63) == 0) atomicAdd(rare->esc_count, (unsigned)__popcll(eb));
-          if (!kEscSweepAll && k < cnt && !win)
+          if (k < cnt && !win)
             mark_escape_tiles(rare->tflag, rare->touched, rare->nchunk + 1, rare->rcov, tl, ng, b[0], b[1], b[2]);
         }
       }
       __syncthreads();
       if (w == (int)blockIdx.x) stamp(SK, 4);
       if (tc.perm && k < cnt) tc.perm[(size_t)w * 256 + balanced_lane(s_rcnt, cnt, res, rrank)] = (unsigned char)q;
-      if constexpr (kAtomicGrid) {  // the box into the dense accumulator, one lane per (node, channel)
-        int lo[3], hi[3];
-        box_unpack(box, lo, hi);
-        const int n1 = hi[1] - lo[1] + 1, n2 = hi[2] - lo[2] + 1, n12 = n1 * n2;
-        const int nvol = (hi[0] - lo[0] + 1) * n12;
-        const float r12 = 1.0f / (float)n12, r2 = 1.0f / (float)n2;
-        for (int e = k; e < 4 * nvol; e += 256) {
-          const int qn = e >> 2, ch = e & 3;
-          const int a = (int)(((float)qn + 0.5f) * r12), rem = qn - a * n12;
-          const int bq = (int)(((float)rem + 0.5f) * r2), c = rem - bq * n2;
-          const int wa = lo[0] + a, wb = lo[1] + bq, wc = lo[2] + c;
-          const int node = (wa * kFW1 + wb) * kFW2 + wc;
-          const int ix = o0 + wa, iy = o1 + wb, iz = o2 + wc;
-          const float val = from_fixed32(s_acc[ch * kFWin + node], S);
-          if (val != 0.f && (unsigned)ix < (unsigned)ng && (unsigned)iy < (unsigned)ng && (unsigned)iz < (unsigned)ng)
-            unsafeAtomicAdd(reinterpret_cast<float*>(rare->gacc + (((size_t)ix * ng + iy) * ng + iz)) + ch, val);
-        }
-      } else {
-        int lo[3], hi[3];
-        box_unpack(box, lo, hi);
-        const int n1 = hi[1] - lo[1] + 1, n2 = hi[2] - lo[2] + 1, n12 = n1 * n2;
-        const int nvol = (hi[0] - lo[0] + 1) * n12;
-        const float r12 = 1.0f / (float)n12, r2 = 1.0f / (float)n2;
-        // the window's slot: the chunk's tile-order id (an ordered record carries it, k_chunk_order)
-        const int cid = (cr.w & 16) ? (int)((unsigned)cr.w >> 5) : w;
-        float4* dst = slots + (size_t)cid * kFWin;
-        for (int qn = k; qn < nvol; qn += 256) {
-          const int a = (int)(((float)qn + 0.5f) * r12), rem = qn - a * n12;
-          const int bq = (int)(((float)rem + 0.5f) * r2), c = rem - bq * n2;
-          const int node = ((lo[0] + a) * kFW1 + lo[1] + bq) * kFW2 + lo[2] + c;
-          const int sl = kOwnerSlots ? slot_loc(lo[0] + a, lo[1] + bq, lo[2] + c) : node;
-          float4 r;
-          r.x = from_fixed32(s_acc[0 * kFWin + node], S);
-          r.y = from_fixed32(s_acc[1 * kFWin + node], S);
-          r.z = from_fixed32(s_acc[2 * kFWin + node], S);
-          r.w = from_fixed32(s_acc[3 * kFWin + node], S);
-          // write-through: a slot is read by other XCDs' grid updates, and a dirty
-          // line left in this XCD's L2 would be written back by the end-of-kernel
-          // release (k_fused 21.9 -> 18.2 us on the lego frame)
-          wt_store4(dst + sl, r);
-        }
+      int lo[3], hi[3];
+      box_unpack(box, lo, hi);
+      const int n1 = hi[1] - lo[1] + 1, n2 = hi[2] - lo[2] + 1, n12 = n1 * n2;
+      const int nvol = (hi[0] - lo[0] + 1) * n12;
+      const float r12 = 1.0f / (float)n12, r2 = 1.0f / (float)n2;
+      // the window's slot: the chunk's tile-order id (an ordered record carries it, k_chunk_order)
+      const int cid = (cr.w & 16) ? (int)((unsigned)cr.w >> 5) : w;
+      float4* dst = slots + (size_t)cid * kFWin;
+      for (int qn = k; qn < nvol; qn += 256) {
+        const int a = (int)(((float)qn + 0.5f) * r12), rem = qn - a * n12;
+        const int bq = (int)(((float)rem + 0.5f) * r2), c = rem - bq * n2;
+        const int node = ((lo[0] + a) * kFW1 + lo[1] + bq) * kFW2 + lo[2] + c;
+        float4 r;
+        r.x = from_fixed32(s_acc[0 * kFWin + node], S);
+        r.y = from_fixed32(s_acc[1 * kFWin + node], S);
+        r.z = from_fixed32(s_acc[2 * kFWin + node], S);
+        r.w = from_fixed32(s_acc[3 * kFWin + node], S);
+        // write-through: a slot is read by other XCDs' grid updates, and a dirty
+        // line left in this XCD's L2 would be written back by the end-of-kernel
+        // release (k_fused 21.9 -> 18.2 us on the lego frame)
+        wt_store4(dst + node, r);
       }
       __syncthreads();  // LDS reuse by the next chunk
     }

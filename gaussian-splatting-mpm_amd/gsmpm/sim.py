@@ -201,7 +201,8 @@ class Simulator:
 
     def profile(self, dt: float, masks):
         """Eager substeps with a hipEvent pair per kernel -> summed ms of
-        (k_p2g, k_grid, k_g2p, binning); fused pipeline: (k_fused, k_grid_f, binning, 0)."""
+        (k_p2g, k_grid, k_g2p, binning); fused pipeline: (k_fused, k_grid_f,
+        binning + the re-binning permute, number of k_grid_f launches)."""
         n = len(masks)
         arr = (ctypes.c_uint32 * max(1, n))(*[int(m) & 0xFFFFFFFF for m in masks])
         out = (ctypes.c_float * 4)()
@@ -211,8 +212,9 @@ class Simulator:
 
     def time_kernels(self, dt: float, mask: int, reps: int = 20):
         """Per-launch ms of (k_p2g, k_grid, k_g2p, binning) -- fused pipeline:
-        (k_fused, k_grid_f, binning, 0) -- from hipEvents around `reps`
-        back-to-back launches of each on this stream; state restored."""
+        (k_fused, k_grid_f, binning, 0: the permute is not timed here and no
+        launch is counted) -- from hipEvents around `reps` back-to-back
+        launches of each on this stream; state restored."""
         out = (ctypes.c_float * 4)()
         check(LIB.gsmpm_mpm_time_kernels(self._h, ctypes.c_float(dt), int(mask) & 0xFFFFFFFF, int(reps), out,
                                          stream_of(self.device)), "gsmpm_mpm_time_kernels")

@@ -220,8 +220,9 @@ int gsmpm_mpm_set_rebin_interval(gsmpm_mpm* h, int32_t substeps);
  * velocity component the previous call ended with (copied to pinned memory
  * without a sync) plus what gravity adds, enough re-binnings that no
  * particle moves more than 0.8 cell between two -- a particle that leaves
- * its chunk's window makes the next grid update sweep every tile -- and at
- * least one per rebin_interval substeps.  out3 = {rebin_interval, auto
+ * its chunk's window (an escape) appends its stencil's tiles to the touched
+ * list and scatters through the global accumulator -- and at least one per
+ * rebin_interval substeps.  out3 = {rebin_interval, auto
  * (0/1), re-binnings chosen for the last call (0: from rebin_interval)};
  * *vmax (may be null) = the last fastest velocity component seen.  No
  * reference counterpart (the reference does not bin, solver.py:27-52). */
@@ -337,7 +338,9 @@ int gsmpm_mpm_world_outputs(gsmpm_mpm* h, float scale, const float center[3], in
  * hipExtLaunchKernel start/stop events (stamped by its own dispatch, the
  * interval rocprofv3 reports); kernel_ms[0..3] = summed time of k_p2g,
  * k_grid, k_g2p and the binning (k_finish_bins, or k_scan_tiles..k_scatter)
- * -- for the fused pipeline {k_fused, k_grid_f, binning, 0}.
+ * -- for the fused pipeline {k_fused, k_grid_f, binning + the re-binning
+ * permute, the number of k_grid_f launches (one per substep; folded: one per
+ * re-binning)}.
  * Synchronises `stream`. */
 int gsmpm_mpm_profile_substeps(gsmpm_mpm* h, float dt, int32_t n_substeps, const uint32_t* bc_active,
                                float* kernel_ms, void* stream);

@@ -133,7 +133,7 @@ def test_fold_escapes(dev):
     the same run to the oracle): most particles leave their chunk window,
     scatter through the escape accumulators (three rotating buffers) and
     gather through the on-demand node evaluation; the unfolded pipeline
-    sweeps every tile instead."""
+    adds the escapes' tiles to the touched list instead."""
     x, cov, vol, kw = _lego(3000, 48)
     c = x.mean(0)
     r = x - c

@@ -1,6 +1,6 @@
 # The re-binning-interval pathology (round-5 verdict item 3): the lego bench
 # at several intervals R, each line with its escapes (particle scatters that
-# left their chunk window -> an all-tile k_grid_f sweep) in the timed frames,
+# left their chunk window -> the global scatter path) in the timed frames,
 # the timed frame and the sim-only frame.  GPU box.  Usage: bash tools/rebin_sweep.sh <outdir>
 set -o pipefail
 O=${1:-gpurun_out/rebin}; mkdir -p $O
