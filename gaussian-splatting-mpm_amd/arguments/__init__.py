@@ -6,7 +6,8 @@ JSON; JSON keys a group does not declare are ignored (which is why lego.json's
 ``model.white_background`` never reaches RenderParams).  A leading
 underscore adds a one-letter short flag.  Additions (all default-off):
 MPMParams.jelly_fcr (fix SURVEY F3), ModelParams.synthetic (generate
-Gaussians when the scene's PLY is absent / an LFS pointer).
+Gaussians when the scene's PLY is absent / an LFS pointer),
+RenderParams.rotate_sh (SH view directions follow particle_R).
 """
 from argparse import ArgumentParser
 
@@ -83,4 +84,5 @@ class RenderParams(ParamGroup):
         self.num_frames = 60
         self.save_pcd = False
         self.save_pcd_interval = 10
+        self.rotate_sh = False  # shade each Gaussian at particle_R d (PhysGaussian's f_0(R^T d))
         super().__init__(parser, "Render Parameters", json_params)

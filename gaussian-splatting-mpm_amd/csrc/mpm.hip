@@ -1365,6 +1365,33 @@ __global__ __launch_bounds__(256) void k_world_out(Particles ps, const int* __re
   for (int i = 0; i < 6; ++i) co[o * 6 + i] = ps.ldc(PCOV + i, (int)o) / ss;  // transform_utils.py:20
 }
 
+// gsmpm_mpm_sh_rotations: particle_R (a cold plane: rows in caller order) as
+// [N,9] records; CONJ: conjugated to A R A^T (render-space means)
+struct Mat9 {
+  float m[9];
+};
+template <bool CONJ>
+__global__ __launch_bounds__(256) void k_sh_rotations(Particles ps, Mat9 A, float* __restrict__ out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= ps.n) return;
+  float R[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = ps.ldc(PR + i, r);
+  if constexpr (CONJ) {
+    float T[9];  // A R
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) T[i * 3 + j] = A.m[i * 3] * R[j] + A.m[i * 3 + 1] * R[3 + j] + A.m[i * 3 + 2] * R[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) R[i * 3 + j] = T[i * 3] * A.m[j * 3] + T[i * 3 + 1] * A.m[j * 3 + 1] + T[i * 3 + 2] * A.m[j * 3 + 2];
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) out[(size_t)r * 9 + i] = R[i];
+}
+
 __global__ void k_grid_get(const float4* __restrict__ src, size_t nn, int which, float* __restrict__ out) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nn; i += (size_t)gridDim.x * blockDim.x) {
     const float4 a = src[i];
@@ -1551,6 +1578,7 @@ struct gsmpm_mpm {
   BcTable* dev_bc = nullptr;
   int n_bc = 0;
   bool has_particles = false;
+  bool has_R = false;  // a gsmpm_mpm_postprocess ran since the particles were set (gsmpm_mpm_sh_rotations)
   hipStream_t cap = nullptr;
   // spatial resort (Morton order of the current cells), every resort_interval substeps
   int resort_interval = 100;
@@ -2990,6 +3018,7 @@ int gsmpm_mpm_set_particles(gsmpm_mpm* h, const float* x, const float* cov6, con
   GSMPM_HIP(hipStreamSynchronize(st));
   *(volatile int*)h->nonfin_host = 0;  // a new state
   h->has_particles = true;
+  h->has_R = false;  // k_init zeroed particle_R
   return GSMPM_OK;
 }
 
@@ -3195,6 +3224,25 @@ int gsmpm_mpm_postprocess(gsmpm_mpm* h, void* stream) {
   GSMPM_REQUIRE(h, "gsmpm_mpm_postprocess: null handle");
   hipLaunchKernelGGL(k_postprocess, dim3(div_up(h->n, 256)), dim3(256), 0, (hipStream_t)stream, particles_of(h),
                      (const int*)h->orig);
+  GSMPM_LAUNCH_CHECK();
+  h->has_R = true;
+  return GSMPM_OK;
+}
+
+int gsmpm_mpm_sh_rotations(gsmpm_mpm* h, const float A[9], float* out, void* stream) {
+  GSMPM_REQUIRE(h && out, "gsmpm_mpm_sh_rotations: null argument");
+  if (h->slab) {
+    set_error("gsmpm_mpm_sh_rotations: not supported on a slab of a multi-GPU domain");
+    return GSMPM_ESTATE;
+  }
+  if (!h->has_particles || !h->has_R) {
+    set_error("gsmpm_mpm_sh_rotations: no gsmpm_mpm_postprocess since the particles were set");
+    return GSMPM_ESTATE;
+  }
+  Mat9 a;
+  for (int i = 0; i < 9; ++i) a.m[i] = A ? A[i] : 0.f;
+  hipLaunchKernelGGL(A ? k_sh_rotations<true> : k_sh_rotations<false>, dim3(div_up(h->n, 256)), dim3(256), 0,
+                     (hipStream_t)stream, particles_of(h), a, out);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }

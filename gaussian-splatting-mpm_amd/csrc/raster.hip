@@ -38,6 +38,13 @@
 //                    contiguous (no global atomics);
 //   k_preprocess_bwd one lane per Gaussian: sums its pair records, then the
 //                    2D-covariance / projection / SH / 3D-covariance adjoints.
+//
+// sh_rotations (gsmpm_raster_args, opt-in; not in upstream or the reference):
+// k_preprocess<ROT> / k_preprocess_bwd<ROT> evaluate each Gaussian's SH at
+// d' = Q d instead of the unit view direction d, Q its row-major 3x3.  The
+// physical Q is particle_R, which the project stores as (U V^T)^T = R^T
+// (utils.py:376-398), so Q d = R^T d: PhysGaussian's f_t(d) = f_0(R^T d).
+// ROT = false is the code that ran before the option existed.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/block/block_radix_sort.hpp>
@@ -108,6 +115,7 @@ struct RasterDev {
   int grid_x, grid_y;
   int tight;  // bin each Gaussian into the tiles its alpha >= 1/255 box reaches (k_preprocess)
   int sh_vec4;  // M == 16 and shs 16-byte aligned: a Gaussian's 48 SH floats as 12 dwordx4 loads
+  const float* sh_rot;  // [P,9] row-major Q per Gaussian (the ROT instantiations), else null
 };
 
 __device__ __forceinline__ void xform4x3(const float* p, const float* m, float o[3]) {
@@ -198,13 +206,34 @@ __device__ __forceinline__ void cov2d(const float* mean, const RasterDev& a, con
 // VEC4: the Gaussian's 48 coefficients arrive as 12 16-byte loads into
 // registers (one lane's 192 B are contiguous; 48 scalar loads made every load
 // instruction touch 64 cache lines); the arithmetic is the same either way
-template <bool VEC4>
+// ROT: the polynomial is evaluated at d' = Q d, Q the Gaussian's 3x3 of
+// RasterDev::sh_rot (no renormalisation: the caller owns Q).  A lane's 9 floats
+// are 36 B apart from its neighbours', so the wave reads one contiguous run
+// and every fetched line is used; 36 B records are only 4-byte aligned, hence
+// dword loads.  ROT = false is the code as it was before the option existed.
+__device__ __forceinline__ void sh_rotate(const float* __restrict__ q, const float d[3], float o[3]) {
+  float Q[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) Q[i] = q[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = Q[i * 3 + 0] * d[0] + Q[i * 3 + 1] * d[1] + Q[i * 3 + 2] * d[2];
+}
+template <bool VEC4, bool ROT>
 __device__ __forceinline__ void sh_rgb(const RasterDev& a, int idx, const float* pos, float rgb[3], unsigned& clamp) {
   float dir[3] = {pos[0] - a.campos[0], pos[1] - a.campos[1], pos[2] - a.campos[2]};
   const float len = sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
   dir[0] /= len;
   dir[1] /= len;
   dir[2] /= len;
+  if constexpr (ROT) {
+    if (a.D > 0) {
+      float dr[3];
+      sh_rotate(a.sh_rot + (size_t)idx * 9, dir, dr);
+      dir[0] = dr[0];
+      dir[1] = dr[1];
+      dir[2] = dr[2];
+    }
+  }
   const float* shg = a.shs + (size_t)idx * a.M * 3;
   float shv[VEC4 ? 48 : 1];
   if constexpr (VEC4) {
@@ -314,6 +343,7 @@ __device__ __forceinline__ void reach_cells(float lo, float hi, int c0, int c1, 
 #include "lsd.h"
 
 // returns the depth bits of a visible Gaussian (tiles word != 0), else 0
+template <bool ROT>
 __device__ __forceinline__ unsigned preprocess_one(const RasterDev& a, int idx, int* __restrict__ radii,
                                                    float* __restrict__ depth, float2* __restrict__ xy,
                                                    float4* __restrict__ conic_o, float4* __restrict__ rgbo,
@@ -358,8 +388,8 @@ __device__ __forceinline__ unsigned preprocess_one(const RasterDev& a, int idx, 
     rgb[1] = a.colors_precomp[(size_t)idx * 3 + 1];
     rgb[2] = a.colors_precomp[(size_t)idx * 3 + 2];
   } else {
-    if (a.sh_vec4) sh_rgb<true>(a, idx, p, rgb, clamp);
-    else sh_rgb<false>(a, idx, p, rgb, clamp);
+    if (a.sh_vec4) sh_rgb<true, ROT>(a, idx, p, rgb, clamp);
+    else sh_rgb<false, ROT>(a, idx, p, rgb, clamp);
   }
   depth[idx] = pv[2];
   radii[idx] = rad;
@@ -389,13 +419,14 @@ __device__ __forceinline__ unsigned preprocess_one(const RasterDev& a, int idx, 
   return __float_as_uint(pv[2]);
 }
 // dst (optional): the depth order's min / max shards (dsort.h)
+template <bool ROT>
 __global__ __launch_bounds__(256) void k_preprocess(RasterDev a, int* __restrict__ radii, float* __restrict__ depth,
                                                     float2* __restrict__ xy, float4* __restrict__ conic_o,
                                                     float4* __restrict__ rgbo, unsigned long long* __restrict__ tiles,
                                                     uint2* __restrict__ rect, unsigned* __restrict__ dst) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   unsigned bits = 0u;
-  if (idx < a.P) bits = preprocess_one(a, idx, radii, depth, xy, conic_o, rgbo, tiles, rect);
+  if (idx < a.P) bits = preprocess_one<ROT>(a, idx, radii, depth, xy, conic_o, rgbo, tiles, rect);
   if (dst) ds_minmax(dst, bits != 0u, bits);  // every lane of the wave: a shuffle reduction
 }
 
@@ -1564,14 +1595,33 @@ __device__ __forceinline__ void dnormvdv(const float v[3], const float dv[3], fl
 
 struct RasterGrads {
   float *dmeans2D, *dcolors, *dopacity, *dmeans3D, *dcov3D, *dsh, *dscales, *drot;
+  float* dshrot;  // dL/dQ [P,9] (ROT instantiation), or null
 };
 
-// computeColorFromSH backward (upstream): dL/dsh and the view-direction term of dL/dmean
+// computeColorFromSH backward (upstream): dL/dsh and the view-direction term of dL/dmean.
+// ROT: the basis and its derivatives are taken at d' = Q d; with g' = dL/dd',
+// dL/dd = Q^T g' goes through dnormvdv and dL/dQ[i][j] = g'_i d_j goes to dq
+// (9 floats, may be null)
+template <bool ROT>
 __device__ void sh_backward(const RasterDev& a, int idx, const float* pos, unsigned clamp, const float dcol[3],
-                            float* dsh, float dmean[3]) {
+                            float* dsh, float dmean[3], float* dq) {
   const float dir_orig[3] = {pos[0] - a.campos[0], pos[1] - a.campos[1], pos[2] - a.campos[2]};
   const float len = sqrtf(dir_orig[0] * dir_orig[0] + dir_orig[1] * dir_orig[1] + dir_orig[2] * dir_orig[2]);
-  const float x = dir_orig[0] / len, y = dir_orig[1] / len, z = dir_orig[2] / len;
+  float x = dir_orig[0] / len, y = dir_orig[1] / len, z = dir_orig[2] / len;
+  float dn[3], Q[9];
+  if constexpr (ROT) {
+    dn[0] = x;
+    dn[1] = y;
+    dn[2] = z;
+    const float* q = a.sh_rot + (size_t)idx * 9;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Q[i] = q[i];
+    if (a.D > 0) {
+      x = Q[0] * dn[0] + Q[1] * dn[1] + Q[2] * dn[2];
+      y = Q[3] * dn[0] + Q[4] * dn[1] + Q[5] * dn[2];
+      z = Q[6] * dn[0] + Q[7] * dn[1] + Q[8] * dn[2];
+    }
+  }
   const float* sh = a.shs + (size_t)idx * a.M * 3;
   float g[3];
   for (int ch = 0; ch < 3; ++ch) g[ch] = ((clamp >> ch) & 1u) ? 0.f : dcol[ch];
@@ -1631,9 +1681,20 @@ __device__ void sh_backward(const RasterDev& a, int idx, const float* pos, unsig
   float* d = dsh + (size_t)idx * a.M * 3;
   for (int k = 0; k < a.M; ++k)
     for (int ch = 0; ch < 3; ++ch) d[k * 3 + ch] = k < used ? coef[k] * g[ch] : 0.f;
-  const float dL_ddir[3] = {dRdx[0] * g[0] + dRdx[1] * g[1] + dRdx[2] * g[2],
-                            dRdy[0] * g[0] + dRdy[1] * g[1] + dRdy[2] * g[2],
-                            dRdz[0] * g[0] + dRdz[1] * g[1] + dRdz[2] * g[2]};
+  float dL_ddir[3] = {dRdx[0] * g[0] + dRdx[1] * g[1] + dRdx[2] * g[2],
+                      dRdy[0] * g[0] + dRdy[1] * g[1] + dRdy[2] * g[2],
+                      dRdz[0] * g[0] + dRdz[1] * g[1] + dRdz[2] * g[2]};
+  if constexpr (ROT) {
+    const float gp[3] = {dL_ddir[0], dL_ddir[1], dL_ddir[2]};  // zero when D == 0 or every channel clamped
+    if (dq) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dq[i * 3 + j] = gp[i] * dn[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dL_ddir[j] = Q[0 * 3 + j] * gp[0] + Q[1 * 3 + j] * gp[1] + Q[2 * 3 + j] * gp[2];
+  }
   float dm[3];
   dnormvdv(dir_orig, dL_ddir, dm);
   for (int q = 0; q < 3; ++q) dmean[q] += dm[q];
@@ -1663,6 +1724,7 @@ __device__ void cov3d_backward(const float* s, float mod, const float* rot, cons
 }
 
 // computeCov2DCUDA + preprocessCUDA backward, one lane per Gaussian.
+template <bool ROT>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* __restrict__ radii,
                                                         const unsigned* __restrict__ offsets,
                                                         const float4* __restrict__ rgbo, const float4* __restrict__ rec,
@@ -1760,10 +1822,13 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* 
   }
   if (a.shs) {
     if (on) {
-      sh_backward(a, idx, m, __float_as_uint(rgbo[idx].w), g + 6, o.dsh, dm);
+      sh_backward<ROT>(a, idx, m, __float_as_uint(rgbo[idx].w), g + 6, o.dsh, dm,
+                       ROT && o.dshrot ? o.dshrot + (size_t)idx * 9 : nullptr);
     } else {
       float* d = o.dsh + (size_t)idx * a.M * 3;
       for (int k = 0; k < a.M * 3; ++k) d[k] = 0.f;
+      if (ROT && o.dshrot)
+        for (int k = 0; k < 9; ++k) o.dshrot[(size_t)idx * 9 + k] = 0.f;
     }
   }
   if (a.scales) {
@@ -2201,6 +2266,7 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* in, float* ou
   GSMPM_REQUIRE(in->shs == nullptr || in->D < 1 || in->M >= (in->D + 1) * (in->D + 1),
                 "gsmpm_raster_forward: too few SH coefficients for sh_degree");
   GSMPM_REQUIRE(!in->prefiltered, "gsmpm_raster_forward: prefiltered=True is not supported (upstream traps too)");
+  GSMPM_REQUIRE(!in->sh_rotations || in->shs, "gsmpm_raster_forward: sh_rotations needs shs");
   hipStream_t st = (hipStream_t)stream;
   TimingGuard tmg(st);
   RasterDev a;
@@ -2221,6 +2287,7 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* in, float* ou
   a.projmatrix = in->projmatrix;
   a.campos = in->campos;
   a.bg = in->bg;
+  a.sh_rot = in->sh_rotations;
   a.tanfovx = in->tanfovx;
   a.tanfovy = in->tanfovy;
   a.focal_x = in->W / (2.0f * in->tanfovx);
@@ -2325,8 +2392,10 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* in, float* ou
                                          : dl && std::strcmp(dl, "bucket") == 0 ? false
                                                                                 : P >= kDlMin);
     const DsortBufs db = dsort_bufs(r);
-    hipLaunchKernelGGL(k_preprocess, dim3(div_up(P, 256)), dim3(256), 0, st, a, out_radii, r->depth, r->xy, r->conic,
-                       r->rgb, r->tiles, r->rect, own_dsort ? db.shard : nullptr);
+    // sh_rotations selects the ROT instantiation; without it the kernel is the one it always was
+    hipLaunchKernelGGL(a.sh_rot ? k_preprocess<true> : k_preprocess<false>, dim3(div_up(P, 256)), dim3(256), 0, st, a,
+                       out_radii, r->depth, r->xy, r->conic, r->rgb, r->tiles, r->rect,
+                       own_dsort ? db.shard : nullptr);
     GSMPM_LAUNCH_CHECK();
     // the index-order scan (offsets) feeds only the backward's record slots
     // and the upstream-keyed path: a depth-ordered forward takes K from the
@@ -2704,6 +2773,14 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* in, float* ou
 int gsmpm_raster_backward(gsmpm_raster* r, const gsmpm_raster_args* in, const int32_t* radii, const float* dL_dcolor,
                           float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                           float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, void* stream) {
+  return gsmpm_raster_backward_rot(r, in, radii, dL_dcolor, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+                                   dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, nullptr, stream);
+}
+
+int gsmpm_raster_backward_rot(gsmpm_raster* r, const gsmpm_raster_args* in, const int32_t* radii,
+                              const float* dL_dcolor, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                              float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                              float* dL_drotations, float* dL_dsh_rotations, void* stream) {
   GSMPM_REQUIRE(r && in && radii && dL_dcolor && dL_dmeans2D && dL_dcolors && dL_dopacity && dL_dmeans3D && dL_dcov3D,
                 "gsmpm_raster_backward: null argument");
   GSMPM_REQUIRE(r->P == in->P && r->W == in->W && r->H == in->H,
@@ -2712,6 +2789,8 @@ int gsmpm_raster_backward(gsmpm_raster* r, const gsmpm_raster_args* in, const in
                 "gsmpm_raster_backward: the context's forward was forward-only (gsmpm_raster_set_forward_only)");
   GSMPM_REQUIRE(!in->shs || dL_dsh, "gsmpm_raster_backward: shs given but no dL_dsh output");
   GSMPM_REQUIRE(!in->scales || (dL_dscales && dL_drotations), "gsmpm_raster_backward: scales given but no outputs");
+  GSMPM_REQUIRE(!in->sh_rotations || in->shs, "gsmpm_raster_backward: sh_rotations needs shs");
+  GSMPM_REQUIRE(!dL_dsh_rotations || in->sh_rotations, "gsmpm_raster_backward: dL_dsh_rotations without sh_rotations");
   hipStream_t st = (hipStream_t)stream;
   if (in->P == 0) return GSMPM_OK;
   RasterDev a;
@@ -2724,6 +2803,7 @@ int gsmpm_raster_backward(gsmpm_raster* r, const gsmpm_raster_args* in, const in
   a.focal_y = in->H / (2.0f * in->tanfovy);
   a.grid_x = r->gx; a.grid_y = r->gy;
   a.tight = 0; a.sh_vec4 = 0;  // forward-only fields
+  a.sh_rot = in->sh_rotations;
   const size_t K = r->K;
   if (K > r->capRec) {
     int rc;
@@ -2753,9 +2833,10 @@ int gsmpm_raster_backward(gsmpm_raster* r, const gsmpm_raster_args* in, const in
     hipLaunchKernelGGL(k_render_bwd, dim3(r->gx, r->gy), dim3(kBlock), 0, st, r->ranges, r->vals_sorted,
                        r->ids_sorted, a.W, a.H, r->gx, r->xy, r->conic, r->rgb, in->bg, r->final_T, r->n_contrib,
                        dL_dcolor, r->rec);
-  RasterGrads o{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations};
-  hipLaunchKernelGGL(k_preprocess_bwd, dim3(div_up(a.P, 256)), dim3(256), 0, st, a, radii, r->offsets, r->rgb,
-                     r->rec, o);
+  RasterGrads o{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+                dL_dsh_rotations};
+  hipLaunchKernelGGL(a.sh_rot ? k_preprocess_bwd<true> : k_preprocess_bwd<false>, dim3(div_up(a.P, 256)), dim3(256), 0,
+                     st, a, radii, r->offsets, r->rgb, r->rec, o);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }
@@ -2825,6 +2906,7 @@ int gsmpm_raster_forward_ws(const gsmpm_raster_args* a, float* out_color, int32_
   GSMPM_REQUIRE(a && workspace && ((uintptr_t)workspace & 255u) == 0,
                 "gsmpm_raster_forward_ws: null argument or workspace not 256-byte aligned");
   GSMPM_REQUIRE(a->P >= 0 && a->W > 0 && a->H > 0, "gsmpm_raster_forward_ws: bad sizes");
+  GSMPM_REQUIRE(!a->sh_rotations || a->shs, "gsmpm_raster_forward_ws: sh_rotations needs shs");
   if (pairs_needed) *pairs_needed = 0;
   WsCount* c = nullptr;
   int rc = ws_count(c);
@@ -2856,6 +2938,7 @@ int gsmpm_raster_forward_async(const gsmpm_raster_args* a, float* out_color, int
                 "gsmpm_raster_forward_async: null argument or workspace not 256-byte aligned");
   GSMPM_REQUIRE(a->P >= 0 && a->W > 0 && a->H > 0 && pairs_cap > 0 && pairs_cap < (1LL << 31),
                 "gsmpm_raster_forward_async: bad sizes or pairs_cap");
+  GSMPM_REQUIRE(!a->sh_rotations || a->shs, "gsmpm_raster_forward_async: sh_rotations needs shs");
   const size_t ntiles = (size_t)div_up(a->W, kBX) * (size_t)div_up(a->H, kBY);
   // the paths whose launch sizes do not depend on the pair count: the default
   // depth-ordered forward with the chunked tile sort (<= kMaxTiles tiles)

@@ -49,6 +49,7 @@ class RasterArgs(ctypes.Structure):
         ("viewmatrix", c_void_p), ("projmatrix", c_void_p), ("campos", c_void_p), ("bg", c_void_p),
         ("tanfovx", ctypes.c_float), ("tanfovy", ctypes.c_float),
         ("prefiltered", ctypes.c_int32),
+        ("sh_rotations", c_void_p),
     ]
 
 
@@ -107,7 +108,8 @@ _SIGS = {
     "gsmpm_mpm_field_width": (ctypes.c_int, [ctypes.c_int32]),
     "gsmpm_mpm_get": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
     "gsmpm_mpm_set": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
-    "gsmpm_mpm_material_mode": (ctypes.c_int, [c_void_p]),
+    "gsmpm_mpm_sh_rotations": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p]),
+    "gsmpm_mpm_material_mode":(ctypes.c_int, [c_void_p]),
     "gsmpm_mpm_set_region_material": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
                                                       ctypes.c_int32, c_void_p]),
     "gsmpm_mpm_set_region_params": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
@@ -154,6 +156,8 @@ _SIGS = {
                                             ctypes.POINTER(ctypes.c_int32), c_void_p]),
     "gsmpm_raster_backward": (ctypes.c_int, [c_void_p, ctypes.POINTER(RasterArgs), c_void_p, c_void_p] +
                               [c_void_p] * 8 + [c_void_p]),
+    "gsmpm_raster_backward_rot": (ctypes.c_int, [c_void_p, ctypes.POINTER(RasterArgs), c_void_p, c_void_p] +
+                                  [c_void_p] * 9 + [c_void_p]),
     "gsmpm_raster_mark_visible": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsmpm_raster_set_forward_only": (ctypes.c_int, [c_void_p, ctypes.c_int32]),
     "gsmpm_raster_pair_counts": (ctypes.c_int, [c_void_p, c_void_p, c_void_p]),

@@ -192,14 +192,19 @@ def _f32(t):
 
 
 def _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
-          sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, prefiltered):
-    """(RasterArgs, the f32 tensors it points into)."""
+          sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, prefiltered,
+          sh_rotations=None):
+    """(RasterArgs, the f32 tensors it points into).  sh_rotations: [P,3,3] or
+    [P,9] row-major, the per-Gaussian Q of gsmpm_raster_args.sh_rotations."""
     means3D = _f32(means3D)
     P = means3D.shape[0] if means3D is not None else 0
     shs, colors_precomp = _f32(shs), _f32(colors_precomp)
     scales, rotations, cov3D_precomp = _f32(scales), _f32(rotations), _f32(cov3D_precomp)
     opacities = _f32(opacities)
     vm, pm, cp, bgc = _f32(viewmatrix), _f32(projmatrix), _f32(campos), _f32(bg)
+    sh_rotations = _f32(sh_rotations)
+    if sh_rotations is not None and sh_rotations.numel() != 9 * P:
+        raise ValueError(f"sh_rotations: expected [{P},3,3] or [{P},9], got {tuple(sh_rotations.shape)}")
     a = _lib.RasterArgs()
     a.P, a.D = P, int(sh_degree)
     a.M = 0 if shs is None else int(shs.reshape(P, -1, 3).shape[1]) if P > 0 else 0
@@ -213,42 +218,49 @@ def _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, 
     a.viewmatrix, a.projmatrix, a.campos, a.bg = ptr(vm), ptr(pm), ptr(cp), ptr(bgc)
     a.tanfovx, a.tanfovy = float(tanfovx), float(tanfovy)
     a.prefiltered = int(bool(prefiltered))
+    a.sh_rotations = ptr(sh_rotations)
     keep = dict(means3D=means3D, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                cov3D_precomp=cov3D_precomp, opacities=opacities, vm=vm, pm=pm, cp=cp, bg=bgc)
+                cov3D_precomp=cov3D_precomp, opacities=opacities, vm=vm, pm=pm, cp=cp, bg=bgc,
+                sh_rotations=sh_rotations)
     return a, keep
 
 
 def backward(context, keep, a, radii, grad_color):
-    """gsmpm_raster_backward on the state of `context`'s forward.  Returns a dict of
+    """gsmpm_raster_backward_rot on the state of `context`'s forward.  Returns a dict of
     means2D [P,3], colors [P,3], opacity [P], means3D [P,3], cov3D [P,6],
-    sh [P,M,3] | None, scales [P,3] | None, rotations [P,4] | None."""
+    sh [P,M,3] | None, scales [P,3] | None, rotations [P,4] | None,
+    sh_rotations [P,3,3] | None (when the forward had sh_rotations)."""
     dev = keep["means3D"].device
     P = a.P
     z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     g = {"means2D": z(P, 3), "colors": z(P, 3), "opacity": z(P), "means3D": z(P, 3), "cov3D": z(P, 6),
          "sh": z(P, a.M, 3) if keep["shs"] is not None else None,
          "scales": z(P, 3) if keep["scales"] is not None else None,
-         "rotations": z(P, 4) if keep["rotations"] is not None else None}
+         "rotations": z(P, 4) if keep["rotations"] is not None else None,
+         "sh_rotations": z(P, 3, 3) if keep.get("sh_rotations") is not None else None}
     grad_color = grad_color.detach().to(torch.float32).contiguous()
     with torch.cuda.device(dev):
-        check(LIB.gsmpm_raster_backward(context.h, ctypes.byref(a), ptr(radii), ptr(grad_color), ptr(g["means2D"]),
-                                        ptr(g["colors"]), ptr(g["opacity"]), ptr(g["means3D"]), ptr(g["cov3D"]),
-                                        ptr(g["sh"]), ptr(g["scales"]), ptr(g["rotations"]), stream_of(dev)),
+        check(LIB.gsmpm_raster_backward_rot(context.h, ctypes.byref(a), ptr(radii), ptr(grad_color),
+                                            ptr(g["means2D"]), ptr(g["colors"]), ptr(g["opacity"]), ptr(g["means3D"]),
+                                            ptr(g["cov3D"]), ptr(g["sh"]), ptr(g["scales"]), ptr(g["rotations"]),
+                                            ptr(g["sh_rotations"]), stream_of(dev)),
               "rasterize_gaussians_backward")
     return g
 
 
 def forward(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
             sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-            scale_modifier=1.0, prefiltered=False, context=None, return_args=False, ws=None):
+            scale_modifier=1.0, prefiltered=False, context=None, return_args=False, ws=None, sh_rotations=None):
     """Returns (num_rendered, color [3,H,W], radii [P] int32) [+ (args, kept tensors)
     when return_args].  `context` (a RasterContext, or a SharedContext) keeps
     this forward's state (for `backward`, or the diagnostics); by default the
-    forward runs in the device's caller-owned Workspace (or `ws`)."""
+    forward runs in the device's caller-owned Workspace (or `ws`).
+    sh_rotations [P,3,3] | [P,9]: evaluate each Gaussian's SH at Q d instead of
+    the view direction d (include/gsmpm.h, gsmpm_raster_args.sh_rotations)."""
     dev = means3D.device
     a, keep = _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx,
                     tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier,
-                    prefiltered)
+                    prefiltered, sh_rotations)
     P = a.P
     color = torch.empty((3, image_height, image_width), dtype=torch.float32, device=dev)
     radii = torch.empty(P, dtype=torch.int32, device=dev)  # k_preprocess writes every entry (0 when culled)
@@ -303,7 +315,8 @@ class AsyncRender:
 
 def forward_async(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
                   sh_degree=0, shs=None, colors_precomp=None, cov3D_precomp=None, scales=None, rotations=None,
-                  scale_modifier=1.0, pairs_cap=None, ws=None, counts=None, color=None, radii=None):
+                  scale_modifier=1.0, pairs_cap=None, ws=None, counts=None, color=None, radii=None,
+                  sh_rotations=None):
     """gsmpm_raster_forward_async: the forward with no host synchronisation
     (the pair count stays on the device; buffers carved for pairs_cap pairs,
     default the workspace's).  Returns an AsyncRender; a frame whose flags
@@ -311,7 +324,8 @@ def forward_async(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_
     rendered again by forward()."""
     dev = means3D.device
     a, keep = _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx,
-                    tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, False)
+                    tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, False,
+                    sh_rotations)
     H, W = int(image_height), int(image_width)
     color = torch.empty((3, H, W), dtype=torch.float32, device=dev) if color is None else color
     radii = torch.empty(a.P, dtype=torch.int32, device=dev) if radii is None else radii

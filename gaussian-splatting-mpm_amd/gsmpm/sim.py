@@ -307,6 +307,24 @@ class Simulator:
                                           ptr(means_out), ptr(cov_out), stream_of(self.device)), "world_outputs")
         return means_out, cov_out
 
+    def sh_rotations(self, A=None, out=None):
+        """gsmpm_mpm_sh_rotations: [N,3,3], the rasterizer's sh_rotations for the
+        last postprocess, in caller order.  A is None: particle_R as stored
+        (= R^T of the polar rotation R, the Q for world-space means).  A given
+        (3x3, means_render = A means_world): A particle_R A^T."""
+        n = self.count
+        out = torch.empty((n, 3, 3), dtype=torch.float32, device=self.device) if out is None else out
+        if n == 0:
+            return out
+        a = None
+        if A is not None:
+            vals = torch.as_tensor(A, dtype=torch.float64).reshape(-1).tolist()
+            if len(vals) != 9:
+                raise ValueError("sh_rotations: A must be 3x3")
+            a = (ctypes.c_float * 9)(*vals)
+        check(LIB.gsmpm_mpm_sh_rotations(self._h, a, ptr(out), stream_of(self.device)), "gsmpm_mpm_sh_rotations")
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             LIB.gsmpm_mpm_destroy(self._h)

@@ -105,8 +105,10 @@ def modify_cam(cam: TinyCam, center_view_world_space, observant_coordinates, dev
 
 
 def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, bg_color, args, rotation_matrices,
-                 pos_center, scaling_modifier=1.0, to_host=True):
-    """main.py:108-157 (render-space transform with scaling_modifier = 1.0)."""
+                 pos_center, scaling_modifier=1.0, to_host=True, sh_rotations=None):
+    """main.py:108-157 (render-space transform with scaling_modifier = 1.0).
+    sh_rotations (--rotate_sh; not in the reference): the per-Gaussian view-direction
+    rotations for the render-space means, MPM_Simulator.sh_rotations(A)."""
     settings = GaussianRasterizationSettings(
         image_height=cam.height, image_width=cam.width, tanfovx=math.tan(cam.FovX * 0.5),
         tanfovy=math.tan(cam.FovY * 0.5), bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=cam.view_mat,
@@ -117,8 +119,18 @@ def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, b
                                                            pos_center), rotation_matrices)
     covs = apply_inverse_cov_rotations(sim_covs / (scaling_modifier * scaling_modifier), rotation_matrices)
     image, _ = rasterizer(means3D=means3D, means2D=None, shs=pc.get_features[mask], colors_precomp=None,
-                          opacities=pc.get_opacity[mask], scales=None, rotations=None, cov3D_precomp=covs)
+                          opacities=pc.get_opacity[mask], scales=None, rotations=None, cov3D_precomp=covs,
+                          sh_rotations=sh_rotations)
     return image.detach().cpu().numpy().transpose(1, 2, 0) if to_host else image
+
+
+def render_space_rotation(rotation_matrices):
+    """The 3x3 A with apply_inverse_rotations(x, rotation_matrices) = A x (host, f64);
+    None when it is the identity, as in every shipped config."""
+    A = np.eye(3)
+    for R in reversed(rotation_matrices):
+        A = R.detach().cpu().numpy().astype(np.float64).T @ A
+    return None if np.array_equal(A, np.eye(3)) else A
 
 
 def save_frame(frame, save_path, fid, save_seq):
@@ -192,7 +204,13 @@ def simulate(model_args, sim_args, render_args):
     solver.set_boundary_conditions(sim_args.boundary_conditions, sim_args)
     solver.add_surface_collider((0.0, 0.0, 0.4), (0.0, 0.0, 1.0))
 
+    # --rotate_sh: shade each Gaussian at particle_R d (f_t(d) = f_0(R^T d), PhysGaussian; the
+    # reference computes particle_R and never reads it).  render_frame's means are
+    # A x sim-space means, A composed here from the scene's rotation matrices.
+    rotate_sh = bool(getattr(render_args, "rotate_sh", False))
+    sh_A = render_space_rotation(rot) if rotate_sh else None
     writer = FrameWriter(out_images, seq)
+    # frame 0 precedes every postprocess: no rotation yet
     writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot, pos_center,
                                to_host=False), 0)
     t0 = time.time()
@@ -208,8 +226,9 @@ def simulate(model_args, sim_args, render_args):
                                                           gaussians._scaling, gaussians._rotation)])
             g2._xyz[mask] = sim_means3D
             g2.save_ply(os.path.join(render_args.output_path, "point_cloud", f"iteration_{fid}", "point_cloud.ply"))
+        sh_rot = solver.sh_rotations(sh_A) if rotate_sh else None
         writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot,
-                                   pos_center, to_host=False), fid)
+                                   pos_center, to_host=False, sh_rotations=sh_rot), fid)
         if fid % 10 == 0 or fid == render_args.num_frames:
             el = time.time() - t0
             print(f"frame {fid}/{render_args.num_frames}  {fid / el:.1f} fps (sim+render+png)", flush=True)

@@ -102,6 +102,14 @@ class MPM_Simulator:
         self.flush()
         self._sim.postprocess()
 
+    def sh_rotations(self, A=None):
+        """[N,3,3] view-direction rotations for the rasterizer's sh_rotations from the
+        last postprocess(): particle_R, or A particle_R A^T when the rendered means
+        are A x the simulated ones (gsmpm_mpm_sh_rotations; not in the reference)."""
+        if self.fitting:
+            raise TypeError("sh_rotations() reads the forward-only state's particle_R; the fitting state has none")
+        return self._sim.sh_rotations(A)
+
     # ----------------------------------------------------------------- BCs --
     def set_boundary_conditions(self, bc_args_arr, sim_args):
         if self.fitting:

@@ -268,6 +268,19 @@ int gsmpm_mpm_postprocess(gsmpm_mpm* h, void* stream);
 int gsmpm_mpm_field_width(int32_t field);
 int gsmpm_mpm_get(gsmpm_mpm* h, int32_t field, float* out, void* stream);
 int gsmpm_mpm_set(gsmpm_mpm* h, int32_t field, const float* in, void* stream);
+/* The per-Gaussian SH view-direction rotations (gsmpm_raster_args.sh_rotations)
+ * that belong to the last gsmpm_mpm_postprocess: out [N,9] row-major, in the
+ * caller's original particle order as gsmpm_mpm_get.  A == NULL: particle_R
+ * unchanged (bit-equal to gsmpm_mpm_get(GSMPM_FIELD_R)).  Otherwise
+ * A particle_R A^T, A (host, row-major) the 3x3 with means_render = A
+ * means_world, as apply_inverse_rotations applies the scene's rotation
+ * matrices: the polar rotation of the A-conjugated F is the conjugated
+ * rotation, so this is the Q of render-space means.  particle_R = R^T, see
+ * gsmpm_raster_args.  No reference counterpart (the reference
+ * computes particle_R and never reads it).  Asynchronous on `stream`.
+ * GSMPM_ESTATE before the first postprocess since the particles were set, and
+ * on a slab handle of a multi-GPU domain (not supported). */
+int gsmpm_mpm_sh_rotations(gsmpm_mpm* h, const float A[9], float* out, void* stream);
 
 /* Per-particle materials (the reference's f32 model.material, dispatched per
  * particle by compute_stress_from_F_trial, utils.py:13-54).  A handle is
@@ -487,7 +500,23 @@ typedef struct {
   const float* bg;           /* [3] */
   float tanfovx, tanfovy;
   int32_t prefiltered;
+  const float* sh_rotations; /* [P,9] row-major or NULL */
 } gsmpm_raster_args;
+/* sh_rotations (no counterpart in the reference, which computes particle_R
+ * and renders the harmonics unrotated; PhysGaussian shades a
+ * Gaussian carried through a local rotation R with f_t(d) = f_0(R^T d)):
+ * one 3x3 Q per Gaussian.  The forward forms d = (mean - campos) / |mean -
+ * campos| as always, then evaluates the SH polynomial, the +0.5, the clamp
+ * and the clamp bits at d' = Q d (d'_i = sum_j Q[i][j] d_j).  No
+ * renormalisation and no orthogonality check: the caller owns Q.  The
+ * physical choice is Q = particle_R: the project stores particle_R =
+ * (U V^T)^T = R^T (utils.py:376-398), so Q d = R^T d; for render-space means
+ * gsmpm_mpm_sh_rotations conjugates it.  NULL is the behaviour without the
+ * option, on the kernels that ran before it existed.  With colors_precomp it
+ * is GSMPM_EINVAL ("sh_rotations needs shs", before any launch); with
+ * sh_degree 0 it is accepted and has no effect.  All three forward forms
+ * honour it; the async form bakes the pointer into a captured graph like the
+ * others. */
 
 int gsmpm_raster_create(gsmpm_raster** out);
 int gsmpm_raster_destroy(gsmpm_raster* r);
@@ -506,6 +535,15 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* a, float* out
 int gsmpm_raster_backward(gsmpm_raster* r, const gsmpm_raster_args* a, const int32_t* radii, const float* dL_dcolor,
                           float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
                           float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, void* stream);
+/* The same with dL_dsh_rotations [P,9] (may be NULL; needs a->sh_rotations),
+ * fully written: with g' = dL/dd' from the polynomial's derivative at d' = Q d,
+ * dL/dQ[i][j] = g'_i d_j (zeros for culled Gaussians and clamped channels),
+ * dL_dsh uses the basis at d', and dL/dd = Q^T g' enters dL_dmeans3D.
+ * gsmpm_raster_backward forwards here with NULL. */
+int gsmpm_raster_backward_rot(gsmpm_raster* r, const gsmpm_raster_args* a, const int32_t* radii,
+                              const float* dL_dcolor, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                              float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                              float* dL_drotations, float* dL_dsh_rotations, void* stream);
 /* Forward-only context (on != 0): gsmpm_raster_forward skips the per-pixel
  * state (final T, last contributor: 8 B a pixel) that only a backward reads,
  * and gsmpm_raster_backward on it fails.  Used for main.py's frames
