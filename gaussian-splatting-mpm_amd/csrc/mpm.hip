@@ -1542,6 +1542,71 @@ __global__ __launch_bounds__(256) void k_fill_vol(const float* __restrict__ x, i
 // =================================================================== host ==
 using namespace gsmpm;
 
+// ---- the memory a handle owns ----------------------------------------------
+// Every buffer is its own hipMalloc / hipHostMalloc, recorded in
+// gsmpm_mpm::mem by alloc() / alloc_host() below: destroy (and so a failed
+// create) frees what the vector holds, and gsmpm_mpm_device_bytes sums the
+// requested sizes per group.
+enum MemGroup { kMemCommon, kMemPhased, kMemFused, kMemFold, kMemPinned };
+enum MemFill { kFillNone, kFillZero, kFillOnes };  // kFillOnes: 0xff bytes
+struct MemRec {
+  void* p;
+  size_t bytes;
+  MemGroup group;
+};
+
+// chunk work lists of one bins parity; both pipelines keep a set per parity
+struct BinLists {
+  int* count = nullptr;    // [ntiles + 1]
+  int* cstart = nullptr;   // [ntiles + 1]
+  int* cbase = nullptr;    // [ntiles + 1]
+  int4* chunk = nullptr;   // [max_chunks] chunk records
+  int* nchunk = nullptr;   // [2] {chunks, touched tiles}
+  // [ntiles] tiles the grid update owns.  Zeroed at create: entries past the
+  // live count are never used, but a read of one must see a valid tile (round
+  // 3's uncommitted three-tiles-per-workgroup k_grid_f read past the count:
+  // hipErrorIllegalAddress)
+  int* touched = nullptr;
+  int* tflag = nullptr;    // [ntiles] membership flags of `touched`
+  int* list = nullptr;     // [np]
+};
+// per-phase pipeline (GSMPM_FLAG_PHASED / KEEP_GRID)
+struct PhasedBufs {
+  // [max_chunks + 1][kWin] per-chunk P2G windows; the last slot (index
+  // max_chunks) is all zero: k_grid reads it for absent tiles
+  float4* slots = nullptr;
+  BinLists b[2];
+};
+// fused G2P2G pipeline (fused.h)
+struct FusedBufs {
+  float4* slots = nullptr;  // [max_chunks + 1][kFWin], the last slot all zero (as PhasedBufs::slots)
+  BinLists b[2];
+  int* cbox[2] = {nullptr, nullptr};     // [max_chunks] per-chunk stencil boxes (fused.h)
+  int* tbox[2] = {nullptr, nullptr};     // [ntiles] per-tile stencil boxes
+  int2* rcov[2] = {nullptr, nullptr};    // [ntiles][kRecStride] cover records per touched position (k_grid_f)
+  int* rbox[2] = {nullptr, nullptr};     // [ntiles][kRecStride] their neighbours' stencil boxes (k_fused writes)
+  int* tpos[2] = {nullptr, nullptr};     // [ntiles] touched position of each tile (0xff bytes, -1: not touched)
+  unsigned char* perm[2] = {nullptr, nullptr};  // [max_chunks][256] lane balance (fused.h)
+  int4* pchunk[2] = {nullptr, nullptr};  // [max_chunks] chunk records in the balanced order (k_fused reads these)
+  float* planes_alt = nullptr;           // the other particle-plane buffer: every binning permutes
+  int* orig_alt = nullptr;               //   storage into bin order, alternating planes / planes_alt
+  int* esc = nullptr;                    // [2] escape flags (alternating per grid update), then the FOLD
+                                         // rotation's [12] (one per phase), one scratch word and the escape count
+  // k_fused's rare arguments (fused.h): [2 bins parities][kRareSlots], slots
+  // 0 / 1 the escape flags of the unfolded pipeline, 2 + r the FOLD phase r
+  // (left zero on a handle without FOLD buffers)
+  FusedRare* rare_dev = nullptr;
+  unsigned* vmax_dev = nullptr;          // [1] max |v| component of the last G2P-only launch (f32 bits)
+  float* vmax_host = nullptr;            // pinned copy, read by the next call
+};
+// the folded grid update: only on a fused handle created with GSMPM_FOLD=1 (h->fold)
+struct FoldBufs {
+  float4* slots2 = nullptr;              // the second slot buffer [max_chunks + 1][kFWin]
+  float4* gacc[2] = {nullptr, nullptr};  // escape accumulators 1 and 2 (0 is the handle's gacc)
+  int* tbox2[2] = {nullptr, nullptr};    // the second tile-box buffer per bins parity
+  float4* esc_nodes = nullptr;           // [np][27] stencil values of particles outside their window
+};
+
 struct gsmpm_mpm {
   gsmpm_mpm_params prm{};
   GridDims g{};
@@ -1560,16 +1625,13 @@ struct gsmpm_mpm {
   int* orig = nullptr;
   float4* gacc = nullptr;   // dense accumulator: outside-grid particles + KEEP_GRID readback
   float4* gvel = nullptr;   // dense v_out
-  float4* slots = nullptr;  // [max_chunks][kWin] per-chunk P2G windows
-  // chunk work lists, one set per parity
-  int* count[2] = {nullptr, nullptr};   // [ntiles + 1]
-  int* cstart[2] = {nullptr, nullptr};  // [ntiles + 1]
-  int* cbase[2] = {nullptr, nullptr};   // [ntiles + 1]
-  int4* chunk[2] = {nullptr, nullptr};  // [max_chunks] chunk records
-  int* nchunk[2] = {nullptr, nullptr};  // [2] {chunks, touched tiles}
-  int* touched[2] = {nullptr, nullptr}; // [ntiles] tiles the grid update owns
-  int* tflag[2] = {nullptr, nullptr};   // [ntiles] membership flags of `touched`
-  int* list[2] = {nullptr, nullptr};    // [np]
+  std::vector<MemRec> mem;  // every allocation the handle owns (alloc / alloc_host / release)
+  // the pipeline's own buffers: `ph` exists on a per-phase handle, `fu` on a
+  // fused one and `fo` on a fused one created with GSMPM_FOLD=1; the others'
+  // pointers stay null
+  PhasedBufs ph;
+  FusedBufs fu;
+  FoldBufs fo;
   int4* scan_part = nullptr;            // [ceil((ntiles + 1) / 1024)] block sums (large-grid binning)
   int* ptile = nullptr;                 // [np]
   int* pslot = nullptr;                 // [np]
@@ -1587,35 +1649,19 @@ struct gsmpm_mpm {
   int* orig_tmp = nullptr;
   uint32_t* sort_keys = nullptr;  // [2][np]
   int* sort_idx = nullptr;        // [2][np]
-  void* sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
-  // fused G2P2G pipeline (fused.h): its own tiling, chunk lists and slots
+  unsigned* sort_tmp = nullptr;   // digit histograms and their row prefixes [2][256][nch], digit totals [256]
+  // fused G2P2G pipeline (fused.h): its own tiling, chunk lists and slots (`fu`)
   bool fused = true;                      // chosen at create (GSMPM_FLAG_PHASED / KEEP_GRID select the per-phase one)
   FTiles ftl{};
-  float4* fslots = nullptr;               // [max_chunks + 1][kFWin]
-  int* fcount[2] = {nullptr, nullptr};
-  int* fcstart[2] = {nullptr, nullptr};
-  int* fcbase[2] = {nullptr, nullptr};
-  int4* fchunk[2] = {nullptr, nullptr};
-  int* fnchunk[2] = {nullptr, nullptr};
-  int* ftouched[2] = {nullptr, nullptr};
-  int* ftflag[2] = {nullptr, nullptr};
-  int* flist[2] = {nullptr, nullptr};
-  int* fesc = nullptr;                    // [2] escape flags (alternating per grid update), then the FOLD
-                                          // rotation's [12] (one per phase) and one scratch word
-  // the folded grid update (fused.h FOLD): launch r of a step call writes slot
-  // buffer r % 2, tile-box buffer r % 2 and escape accumulator r % 3
+  // the folded grid update (fused.h FOLD, buffers in `fo`): launch r of a step
+  // call writes slot buffer r % 2, tile-box buffer r % 2 and escape accumulator r % 3
   // GSMPM_FOLD=1 at create (A/B, off by default): measured and rejected in
   // round 6 -- the folded staging costs k_fused more than k_grid_f + its
   // boundary
   bool fold = false;
-  float4* fslots2 = nullptr;              // the second slot buffer [max_chunks + 1][kFWin]
-  float4* gacc_f[3] = {nullptr, nullptr, nullptr};  // escape accumulators ([0] = gacc)
-  int* ftbox2[2] = {nullptr, nullptr};    // the second tile-box buffer per bins parity
-  float4* fesc_nodes = nullptr;           // [np][27] stencil values of particles outside their window
   // adaptive re-binning (round 6): the re-binnings of a step call are chosen
   // from the particles' fastest velocity at the end of the call before
-  // (vmax_dev, copied to vmax_host without a sync), so that no particle
+  // (fu.vmax_dev, copied to fu.vmax_host without a sync), so that no particle
   // moves more than ~0.8 of a cell between two re-binnings -- the moves that
   // leave a chunk's window and make the next grid update sweep every tile
   // (DESIGN.md §3.4).  rebin_interval is then the longest spacing allowed.
@@ -1624,29 +1670,18 @@ struct gsmpm_mpm {
   // at the default interval the extra re-binnings of the fall cost the
   // 20-frame bench 2-3 %
   bool rebin_auto = false;
-  unsigned* vmax_dev = nullptr;           // [1] max |v| component of the last G2P-only launch (f32 bits)
-  float* vmax_host = nullptr;             // pinned copy, read by the next call
   int rebin_m = 0;                        // re-binnings of the current call (0: from rebin_interval)
-  int* fcbox[2] = {nullptr, nullptr};     // [max_chunks] per-chunk stencil boxes (fused.h)
-  int* ftbox[2] = {nullptr, nullptr};     // [ntiles] per-tile stencil boxes
-  int2* frcov[2] = {nullptr, nullptr};    // [ntiles][kRecStride] cover records per touched position (k_grid_f)
-  int* frbox[2] = {nullptr, nullptr};     // [ntiles][kRecStride] their neighbours' stencil boxes (k_fused writes)
-  int* ftpos[2] = {nullptr, nullptr};     // [ntiles] touched position of each tile
-  unsigned char* fperm[2] = {nullptr, nullptr};  // [max_chunks][256] lane balance (fused.h); null: off
   bool lane_balance = true;               // GSMPM_LANE_BALANCE=0 turns it off (A/B)
   bool fuse_permute = true;               // GSMPM_FUSE_PERMUTE=0: separate k_permute (A/B)
   bool cover_records = true;              // GSMPM_COVER_RECORDS=0: k_grid_f reads the tile tables only (A/B)
   int fused_wgs = 1024;                   // k_fused grid cap: the workgroups resident at once x rounds of full chunks, <= 6 (init)
   // Chunk order (k_chunk_order): k_fused's workgroup b takes the chunk at
-  // position b of a size-balanced order instead of chunk b, so the
-  // workgroups that share a CU carry about equal particle counts.
+  // position b of a size-balanced order (fu.pchunk) instead of chunk b, so
+  // the workgroups that share a CU carry about equal particle counts.
   // On for one resident round of workgroups (init); GSMPM_CHUNK_ORDER=0 / 1
   // forces tile order / the balanced order (A/B)
   bool chunk_order = true;
   int ncu = 256;                          // CUs of the device (the order's tier width)
-  int4* fpchunk[2] = {nullptr, nullptr};  // [max_chunks] chunk records in that order (k_fused reads these)
-  float* planes_alt = nullptr;            // the other particle-plane buffer: every binning permutes
-  int* orig_alt = nullptr;                //   storage into bin order, alternating planes / planes_alt
   int fbpar = 0;                          // parity of the bins the next k_fused reads
   int fep = 0;                            // escape flag the next P2G raises
   int rebin_interval = 10;                // substeps between re-binnings (fused pipeline; set by material at create)
@@ -1710,10 +1745,7 @@ struct gsmpm_mpm {
   int* nonfin_host = nullptr;                // non-finite particle state seen: x, or P2G's m / v / C / stress
                                              // (pinned, device-mapped; sticky)
   int* nonfin_dev = nullptr;                 // its device address
-  // k_fused's rare arguments (fused.h): [2 bins parities][kRareSlots], slots
-  // 0 / 1 the escape flags of the unfolded pipeline, 2 + r the FOLD phase r
-  FusedRare* frare_dev = nullptr;
-  FusedRare frare_host[2 * 14] = {};         // what frare_dev holds
+  FusedRare frare_host[2 * 14] = {};         // what fu.rare_dev holds
   float* mig_send[2] = {nullptr, nullptr};   // fixed-size payloads: header + [NMIG][mig_cap]
   float* mig_recv[2] = {nullptr, nullptr};
   int mig_cap = 0;                           // leavers one migration may send one way (all ranks agree)
@@ -1726,13 +1758,64 @@ struct gsmpm_mpm {
   long s_host_syncs = 0, s_calls = 0;        // host syncs inside gsmpm_mpm_slab_step, step calls
   long s_since = 0;                          // substeps since the last migration
   bool s_graph = true;                       // capture RCCL step calls in hipGraphs (GSMPM_SLAB_GRAPH=0: eager)
-  float* x_host = nullptr;                   // CALLBACK transport: pinned staging of the exchanged buffers
+  char* x_host = nullptr;                    // CALLBACK transport: pinned staging of the exchanged buffers
   size_t x_host_cap = 0;
 };
 
 namespace gsmpm {
 static thread_local std::string g_err;
 void set_error(const std::string& m) { g_err = m; }
+
+// One tracked buffer of `count` elements; fill: its initial bytes, from
+// element `fill_from` on (the "zero only the last slot" case).  A buffer that
+// failed its memset is already recorded, so the handle's destroy frees it.
+template <typename T>
+static hipError_t alloc(gsmpm_mpm* h, T** p, size_t count, MemGroup group, MemFill fill = kFillNone,
+                        size_t fill_from = 0) {
+  void* q = nullptr;
+  const hipError_t e = hipMalloc(&q, sizeof(T) * count);
+  if (e != hipSuccess) return e;
+  h->mem.push_back(MemRec{q, sizeof(T) * count, group});
+  *p = static_cast<T*>(q);
+  if (fill == kFillNone) return hipSuccess;
+  return hipMemset(*p + fill_from, fill == kFillZero ? 0 : 0xff, sizeof(T) * (count - fill_from));
+}
+// pinned host memory (hipHostMalloc flags)
+template <typename T>
+static hipError_t alloc_host(gsmpm_mpm* h, T** p, size_t count, unsigned flags = hipHostMallocDefault) {
+  void* q = nullptr;
+  const hipError_t e = hipHostMalloc(&q, sizeof(T) * count, flags);
+  if (e != hipSuccess) return e;
+  h->mem.push_back(MemRec{q, sizeof(T) * count, kMemPinned});
+  *p = static_cast<T*>(q);
+  return hipSuccess;
+}
+static void free_rec(const MemRec& r) { (void)(r.group == kMemPinned ? hipHostFree(r.p) : hipFree(r.p)); }
+// frees one buffer ahead of destroy (the few that are regrown); a null *p is fine
+template <typename T>
+static void release(gsmpm_mpm* h, T** p) {
+  for (size_t i = 0; i < h->mem.size(); ++i)
+    if (*p && h->mem[i].p == *p) {
+      free_rec(h->mem[i]);
+      h->mem.erase(h->mem.begin() + i);
+      break;
+    }
+  *p = nullptr;
+}
+
+// one parity's lists of either pipeline; count, nchunk, tflag and touched start zeroed
+static hipError_t alloc_bin_lists(gsmpm_mpm* h, BinLists& b, int ntiles, int max_chunks, MemGroup group) {
+  const size_t E = (size_t)ntiles + 1;
+  hipError_t e = alloc(h, &b.count, E, group, kFillZero);
+  if (e == hipSuccess) e = alloc(h, &b.cstart, E, group);
+  if (e == hipSuccess) e = alloc(h, &b.cbase, E, group);
+  if (e == hipSuccess) e = alloc(h, &b.chunk, (size_t)max_chunks, group);
+  if (e == hipSuccess) e = alloc(h, &b.nchunk, 2, group, kFillZero);
+  if (e == hipSuccess) e = alloc(h, &b.touched, (size_t)ntiles, group, kFillZero);
+  if (e == hipSuccess) e = alloc(h, &b.tflag, (size_t)ntiles, group, kFillZero);
+  if (e == hipSuccess) e = alloc(h, &b.list, (size_t)h->np, group);
+  return e;
+}
 
 static Particles particles_of(gsmpm_mpm* h) {
   return Particles{h->planes, h->n, h->np, h->cold, h->slab ? h->d_n : nullptr};
@@ -1742,17 +1825,24 @@ static Particles particles_of(gsmpm_mpm* h) {
 static int live_rows(const gsmpm_mpm* h) { return h->slab ? h->np : h->n; }
 static const int* nlive_of(const gsmpm_mpm* h) { return h->slab ? h->d_n : nullptr; }
 
-static ChunkIn chunk_in(gsmpm_mpm* h, int c) {
-  return ChunkIn{h->count[c], h->cbase[c], h->chunk[c], h->nchunk[c], h->list[c], h->touched[c]};
+// the common part of both pipelines' ChunkIn / ChunkOut: one parity's lists
+// (`records`: the chunk records the kernel walks)
+static ChunkIn chunk_in(const BinLists& b, int4* records) {
+  return ChunkIn{b.count, b.cbase, records, b.nchunk, b.list, b.touched};
 }
-static ChunkOut chunk_out(gsmpm_mpm* h, int c) {
-  return ChunkOut{h->cstart[c], h->cbase[c], h->chunk[c], h->nchunk[c], h->tflag[c], h->touched[c]};
+static ChunkOut chunk_out(const BinLists& b) {
+  return ChunkOut{b.cstart, b.cbase, b.chunk, b.nchunk, b.tflag, b.touched};
 }
+
+static ChunkIn chunk_in(gsmpm_mpm* h, int c) { return chunk_in(h->ph.b[c], h->ph.b[c].chunk); }
+static ChunkOut chunk_out(gsmpm_mpm* h, int c) { return chunk_out(h->ph.b[c]); }
 static BinOut bin_out(gsmpm_mpm* h, int c) {
-  return BinOut{h->count[c], h->ptile, h->pslot, h->tflag[c], h->tl.td, h->tl.ntiles};
+  return BinOut{h->ph.b[c].count, h->ptile, h->pslot, h->ph.b[c].tflag, h->tl.td, h->tl.ntiles};
 }
 
 static bool use_fused(const gsmpm_mpm* h) { return h->fused; }
+// the lists of the pipeline the handle runs
+static const BinLists& bin_lists(const gsmpm_mpm* h, int c) { return use_fused(h) ? h->fu.b[c] : h->ph.b[c]; }
 
 // template code of the P2G kernels: the create-time material, or the mixed dispatch
 static int kernel_code(const gsmpm_mpm* h) { return h->mixed ? kMatMixed : h->mat_kernel; }
@@ -1763,30 +1853,33 @@ static MatIds<kMatMixed> mat_ids_of(gsmpm_mpm* h) {
 
 // the chunk records k_fused walks: the balanced order (k_chunk_order) or tile order
 static int4* fused_records(gsmpm_mpm* h, int c) {
-  return h->chunk_order ? h->fpchunk[c] : h->fchunk[c];
+  return h->chunk_order ? h->fu.pchunk[c] : h->fu.b[c].chunk;
 }
 static ChunkIn chunk_in_f(gsmpm_mpm* h, int c) {
-  ChunkIn ci{h->fcount[c], h->fcbase[c], fused_records(h, c), h->fnchunk[c], h->flist[c], h->ftouched[c]};
+  ChunkIn ci = chunk_in(h->fu.b[c], fused_records(h, c));
   if (h->cover_records) {
-    ci.rcov = h->frcov[c];
-    ci.rbox = h->frbox[c];
+    ci.rcov = h->fu.rcov[c];
+    ci.rbox = h->fu.rbox[c];
   }
   return ci;
 }
 static ChunkOut chunk_out_f(gsmpm_mpm* h, int c) {
-  ChunkOut co{h->fcstart[c], h->fcbase[c], h->fchunk[c], h->fnchunk[c], h->ftflag[c], h->ftouched[c]};
-  co.rcov = h->frcov[c];
-  co.tpos = h->ftpos[c];
+  ChunkOut co = chunk_out(h->fu.b[c]);
+  co.rcov = h->fu.rcov[c];
+  co.tpos = h->fu.tpos[c];
   co.td1 = h->ftl.td1;
   co.td2 = h->ftl.td2;
   return co;
 }
 static Touch touch_f(gsmpm_mpm* h, int c) {
-  return Touch{h->ftflag[c], h->ftouched[c], h->fnchunk[c], h->fchunk[c], h->fcbox[c], h->ftbox[c],
-               h->lane_balance ? h->fperm[c] : nullptr, h->frcov[c],
-               h->cover_records ? h->ftpos[c] : nullptr, h->frbox[c]};
+  const BinLists& b = h->fu.b[c];
+  return Touch{b.tflag, b.touched, b.nchunk, b.chunk, h->fu.cbox[c], h->fu.tbox[c],
+               h->lane_balance ? h->fu.perm[c] : nullptr, h->fu.rcov[c],
+               h->cover_records ? h->fu.tpos[c] : nullptr, h->fu.rbox[c]};
 }
-static BinOutF bin_out_f(gsmpm_mpm* h, int c) { return BinOutF{h->fcount[c], h->ptile, h->pslot, h->ftflag[c], h->ftl}; }
+static BinOutF bin_out_f(gsmpm_mpm* h, int c) {
+  return BinOutF{h->fu.b[c].count, h->ptile, h->pslot, h->fu.b[c].tflag, h->ftl};
+}
 // k_finish_bins / the scan kernels only use ntiles and max_chunks of a Tiles
 static Tiles ftiles_flat(const gsmpm_mpm* h) { return Tiles{h->ftl.td0, h->ftl.ntiles, h->ftl.max_chunks}; }
 
@@ -1809,10 +1902,10 @@ template <int MAT>
 static void launch_p2g(gsmpm_mpm* h, int c, uint32_t mask, float dt, hipStream_t st, const hipEvent_t* ev) {
   if constexpr (MAT == kMatMixed)
     launch(ev, k_p2g_mixed, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
-           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->slots, h->gacc, h->nonfin_dev, mat_ids_of(h));
+           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->ph.slots, h->gacc, h->nonfin_dev, mat_ids_of(h));
   else
     launch(ev, k_p2g<MAT>, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
-           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->slots, h->gacc, h->nonfin_dev);
+           (const BcTable*)h->dev_bc, mask, dt, h->mc, h->ph.slots, h->gacc, h->nonfin_dev);
 }
 
 // counts -> list offsets + chunk list, then the per-tile lists
@@ -1837,7 +1930,7 @@ static int finish_bins_on(gsmpm_mpm* h, const Tiles& tl, const int* count, const
   return GSMPM_OK;
 }
 static int finish_binning(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t* ev = nullptr) {
-  return finish_bins_on(h, h->tl, h->count[c], chunk_out(h, c), h->list[c], st, ev);
+  return finish_bins_on(h, h->tl, h->ph.b[c].count, chunk_out(h, c), h->ph.b[c].list, st, ev);
 }
 // Chunk order (the fused bins of parity c): one workgroup ranks the chunks by
 // particle count, largest first, and lays the ranks out in tiers of ncu
@@ -1978,16 +2071,16 @@ static int order_chunks_f(gsmpm_mpm* h, int c, hipStream_t st) {
   if (!h->chunk_order) return GSMPM_OK;  // multi-round grids keep the tile order
   // the XCD form where k_fused's grid is a multiple of 8 and the chunks fit its LDS tables
   if (GSMPM_CHUNK_XCD && kGridGroup > 0 && std::min(h->ftl.max_chunks, h->fused_wgs) % 8 == 0)
-    launch(nullptr, k_chunk_order_xcd, dim3(1), dim3(1024), st, (const int4*)h->fchunk[c], (const int*)h->fnchunk[c],
-           (const int*)h->ftpos[c], h->ftl.ntiles, h->fpchunk[c], h->ncu);
+    launch(nullptr, k_chunk_order_xcd, dim3(1), dim3(1024), st, (const int4*)h->fu.b[c].chunk,
+           (const int*)h->fu.b[c].nchunk, (const int*)h->fu.tpos[c], h->ftl.ntiles, h->fu.pchunk[c], h->ncu);
   else
-    launch(nullptr, k_chunk_order, dim3(1), dim3(1024), st, (const int4*)h->fchunk[c], (const int*)h->fnchunk[c],
-           h->fpchunk[c], h->ncu);
+    launch(nullptr, k_chunk_order, dim3(1), dim3(1024), st, (const int4*)h->fu.b[c].chunk,
+           (const int*)h->fu.b[c].nchunk, h->fu.pchunk[c], h->ncu);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }
 static int finish_binning_f(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t* ev = nullptr) {
-  const int rc = finish_bins_on(h, ftiles_flat(h), h->fcount[c], chunk_out_f(h, c), h->flist[c], st, ev);
+  const int rc = finish_bins_on(h, ftiles_flat(h), h->fu.b[c].count, chunk_out_f(h, c), h->fu.b[c].list, st, ev);
   return rc ? rc : order_chunks_f(h, c, st);
 }
 // the binning of parity c and the storage permutation into its order: one
@@ -1996,16 +2089,17 @@ static int finish_binning_f(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_
 static int permute_to_bins(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t* ev);
 static int rebin_permute_f(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t* ev = nullptr, bool vc_live = true) {
   if (bins_fused(ftiles_flat(h)) && h->fuse_permute) {
-    const BinPermute bp{h->planes, h->planes_alt, h->np, h->orig, h->orig_alt, (vc_live || GSMPM_STORE_VC) ? 0 : 1};
-    int rc = finish_bins_on(h, ftiles_flat(h), h->fcount[c], chunk_out_f(h, c), h->flist[c], st, ev, bp);
+    const BinPermute bp{h->planes, h->fu.planes_alt, h->np,
+                        h->orig,   h->fu.orig_alt,   (vc_live || GSMPM_STORE_VC) ? 0 : 1};
+    int rc = finish_bins_on(h, ftiles_flat(h), h->fu.b[c].count, chunk_out_f(h, c), h->fu.b[c].list, st, ev, bp);
     if (!rc) rc = order_chunks_f(h, c, st);
     if (rc) return rc;
     if (ev) {  // the permute's timing pair: nothing left to time
       GSMPM_HIP(hipEventRecord(ev[2], st));
       GSMPM_HIP(hipEventRecord(ev[3], st));
     }
-    std::swap(h->planes, h->planes_alt);
-    std::swap(h->orig, h->orig_alt);
+    std::swap(h->planes, h->fu.planes_alt);
+    std::swap(h->orig, h->fu.orig_alt);
     return GSMPM_OK;
   }
   int rc = finish_binning_f(h, c, st, ev);
@@ -2016,11 +2110,11 @@ static int rebin_permute_f(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t
 // tile): planes / orig gathered into the other buffer, which becomes current.
 static int permute_to_bins(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t* ev) {
   launch(ev, k_permute, dim3(std::max(1, div_up(live_rows(h), 256)), NPLANES + 1), dim3(256), st,
-         (const float*)h->planes, h->planes_alt, h->n, nlive_of(h), h->np, (const int*)h->flist[c],
-         (const int*)h->orig, h->orig_alt);
+         (const float*)h->planes, h->fu.planes_alt, h->n, nlive_of(h), h->np, (const int*)h->fu.b[c].list,
+         (const int*)h->orig, h->fu.orig_alt);
   GSMPM_LAUNCH_CHECK();
-  std::swap(h->planes, h->planes_alt);
-  std::swap(h->orig, h->orig_alt);
+  std::swap(h->planes, h->fu.planes_alt);
+  std::swap(h->orig, h->fu.orig_alt);
   return GSMPM_OK;
 }
 
@@ -2028,9 +2122,9 @@ static int permute_to_bins(gsmpm_mpm* h, int c, hipStream_t st, const hipEvent_t
 // x and permute storage into that bin order.
 static int rebin_f(gsmpm_mpm* h, hipStream_t st) {
   const int c = h->fbpar;
-  GSMPM_HIP(hipMemsetAsync(h->fcount[c], 0, sizeof(int) * (h->ftl.ntiles + 1), st));
-  GSMPM_HIP(hipMemsetAsync(h->ftflag[c], 0, sizeof(int) * h->ftl.ntiles, st));
-  GSMPM_HIP(hipMemsetAsync(h->fnchunk[c], 0, sizeof(int) * 2, st));
+  GSMPM_HIP(hipMemsetAsync(h->fu.b[c].count, 0, sizeof(int) * (h->ftl.ntiles + 1), st));
+  GSMPM_HIP(hipMemsetAsync(h->fu.b[c].tflag, 0, sizeof(int) * h->ftl.ntiles, st));
+  GSMPM_HIP(hipMemsetAsync(h->fu.b[c].nchunk, 0, sizeof(int) * 2, st));
   hipLaunchKernelGGL(k_bin_all_f, dim3(std::max(1, div_up(live_rows(h), 256))), dim3(256), 0, st, particles_of(h), h->g,
                      bin_out_f(h, c));
   GSMPM_LAUNCH_CHECK();
@@ -2040,9 +2134,9 @@ static int rebin_f(gsmpm_mpm* h, hipStream_t st) {
 // (Re)build the per-phase pipeline's chunk lists of parity `cur_box` from the current x.
 static int rebin_phased(gsmpm_mpm* h, hipStream_t st) {
   const int c = h->cur_box;
-  GSMPM_HIP(hipMemsetAsync(h->count[c], 0, sizeof(int) * (h->tl.ntiles + 1), st));
-  GSMPM_HIP(hipMemsetAsync(h->tflag[c], 0, sizeof(int) * h->tl.ntiles, st));
-  GSMPM_HIP(hipMemsetAsync(h->nchunk[c], 0, sizeof(int) * 2, st));
+  GSMPM_HIP(hipMemsetAsync(h->ph.b[c].count, 0, sizeof(int) * (h->tl.ntiles + 1), st));
+  GSMPM_HIP(hipMemsetAsync(h->ph.b[c].tflag, 0, sizeof(int) * h->tl.ntiles, st));
+  GSMPM_HIP(hipMemsetAsync(h->ph.b[c].nchunk, 0, sizeof(int) * 2, st));
   hipLaunchKernelGGL(k_bin_all, dim3(div_up(h->n, 256)), dim3(256), 0, st, particles_of(h), h->g, h->tl,
                      bin_out(h, c));
   GSMPM_LAUNCH_CHECK();
@@ -2085,7 +2179,8 @@ static int substep_begin(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream
 static int substep_end(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream_t st, const hipEvent_t* e8) {
   const int nx = c ^ 1;
   launch(e8 ? e8 + 2 : nullptr, k_grid, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
-         (const float4*)h->slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), bin_out(h, nx));
+         (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask),
+         bin_out(h, nx));
   GSMPM_LAUNCH_CHECK();
   launch(e8 ? e8 + 4 : nullptr, k_g2p, dim3(g2p_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl,
          chunk_in(h, c), bin_out(h, nx), (const float4*)h->gvel, dt);
@@ -2130,11 +2225,14 @@ static int fused_grid(gsmpm_mpm* h) { return std::min(h->ftl.max_chunks, h->fuse
 constexpr int kRareSlots = 14;  // per bins parity: 2 unfolded escape flags + 12 FOLD phases
 constexpr int kFoldPhases = 12;
 // FOLD phase r's buffers (launch r of a step call, fused.h FusedRare)
-static float4* fold_slots(gsmpm_mpm* h, int r) { return (r & 1) ? h->fslots2 : h->fslots; }
-static int* fold_tbox(gsmpm_mpm* h, int c, int r) { return (r & 1) ? h->ftbox2[c] : h->ftbox[c]; }
-static int* fold_flag(gsmpm_mpm* h, int r) { return h->fesc + 2 + ((r % kFoldPhases) + kFoldPhases) % kFoldPhases; }
-static float4* fold_gacc(gsmpm_mpm* h, int r) { return h->gacc_f[((r % 3) + 3) % 3]; }
-static int* fold_scratch(gsmpm_mpm* h) { return h->fesc + 2 + kFoldPhases; }
+static float4* fold_slots(gsmpm_mpm* h, int r) { return (r & 1) ? h->fo.slots2 : h->fu.slots; }
+static int* fold_tbox(gsmpm_mpm* h, int c, int r) { return (r & 1) ? h->fo.tbox2[c] : h->fu.tbox[c]; }
+static int* fold_flag(gsmpm_mpm* h, int r) { return h->fu.esc + 2 + ((r % kFoldPhases) + kFoldPhases) % kFoldPhases; }
+static float4* fold_gacc(gsmpm_mpm* h, int r) {
+  const int i = ((r % 3) + 3) % 3;
+  return i ? h->fo.gacc[i - 1] : h->gacc;
+}
+static int* fold_scratch(gsmpm_mpm* h) { return h->fu.esc + 2 + kFoldPhases; }
 
 // rare slot: 0 / 1 the unfolded pipeline's escape flag e; 2 + r the FOLD phase r
 static FusedRare rare_of(gsmpm_mpm* h, int c, int slot) {
@@ -2143,18 +2241,18 @@ static FusedRare rare_of(gsmpm_mpm* h, int c, int slot) {
   const int ph = slot - 2;
   r.bo = bin_out_f(h, c ^ 1);
   r.gacc = fold ? fold_gacc(h, ph) : h->gacc;
-  r.esc = fold ? fold_flag(h, ph) : h->fesc + slot;
+  r.esc = fold ? fold_flag(h, ph) : h->fu.esc + slot;
   r.drift = h->slab ? h->s_drift : nullptr;
   r.nonfin = h->slab ? h->s_drift + SF_NONFIN : h->nonfin_dev;
   r.bct = h->dev_bc;
-  r.tflag = h->ftflag[c];
-  r.touched = h->ftouched[c];
-  r.nchunk = h->fnchunk[c];
+  r.tflag = h->fu.b[c].tflag;
+  r.touched = h->fu.b[c].touched;
+  r.nchunk = h->fu.b[c].nchunk;
   r.chunk = fused_records(h, c);
-  r.rcov = h->frcov[c];
-  r.tbox = fold ? fold_tbox(h, c, ph) : h->ftbox[c];
-  r.tpos = h->cover_records ? h->ftpos[c] : nullptr;
-  r.rbox = h->frbox[c];
+  r.rcov = h->fu.rcov[c];
+  r.tbox = fold ? fold_tbox(h, c, ph) : h->fu.tbox[c];
+  r.tpos = h->cover_records ? h->fu.tpos[c] : nullptr;
+  r.rbox = h->fu.rbox[c];
   if (fold) {
     r.slots_prev = fold_slots(h, ph + 1);  // (r - 1) mod 2
     r.tbox_prev = fold_tbox(h, c, ph + 1);
@@ -2165,9 +2263,9 @@ static FusedRare rare_of(gsmpm_mpm* h, int c, int slot) {
     r.esc_clr = fold_flag(h, ph - 3);
   }
   for (int d = 0; d < 3; ++d) r.grav[d] = (float)h->prm.gravity[d];
-  r.esc_count = reinterpret_cast<unsigned*>(h->fesc + 3 + kFoldPhases);
-  r.esc_nodes = h->fesc_nodes;
-  r.vmax = h->slab ? nullptr : h->vmax_dev;
+  r.esc_count = reinterpret_cast<unsigned*>(h->fu.esc + 3 + kFoldPhases);
+  r.esc_nodes = h->fo.esc_nodes;
+  r.vmax = h->slab ? nullptr : h->fu.vmax_dev;
   return r;
 }
 // k_fused's rare arguments in device memory, rewritten (outside captures,
@@ -2176,6 +2274,7 @@ static FusedRare rare_of(gsmpm_mpm* h, int c, int slot) {
 static int sync_rare(gsmpm_mpm* h, hipStream_t st) {
   bool dirty = false;
   for (int i = 0; i < 2 * kRareSlots; ++i) {
+    if (i % kRareSlots >= 2 && !h->fold) continue;  // the FOLD phases' slots stay zero: no launch reads them
     const FusedRare r = rare_of(h, i / kRareSlots, i % kRareSlots);
     if (std::memcmp(&r, &h->frare_host[i], sizeof(r)) != 0) {
       h->frare_host[i] = r;
@@ -2184,7 +2283,7 @@ static int sync_rare(gsmpm_mpm* h, hipStream_t st) {
   }
   if (!dirty) return GSMPM_OK;
   GSMPM_REQUIRE(!h->capturing, "k_fused's rare arguments changed inside a capture");
-  GSMPM_HIP(hipMemcpyAsync(h->frare_dev, h->frare_host, sizeof(h->frare_host), hipMemcpyHostToDevice, st));
+  GSMPM_HIP(hipMemcpyAsync(h->fu.rare_dev, h->frare_host, sizeof(h->frare_host), hipMemcpyHostToDevice, st));
   return GSMPM_OK;
 }
 // one k_fused launch: bins parity c, rare slot `slot`, chunk windows stored to
@@ -2201,11 +2300,11 @@ static void launch_fused_t(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, c
   if constexpr (MAT == kMatMixed)
     launch(ev, k_fused_mixed<MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
            chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
-           xlo, xhi, (const FusedRare*)(h->frare_dev + f.c * kRareSlots + f.slot), f.mask_prev, mat_ids_of(h));
+           xlo, xhi, (const FusedRare*)(h->fu.rare_dev + f.c * kRareSlots + f.slot), f.mask_prev, mat_ids_of(h));
   else
     launch(ev, k_fused<MAT, MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
            chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
-           xlo, xhi, (const FusedRare*)(h->frare_dev + f.c * kRareSlots + f.slot), f.mask_prev);
+           xlo, xhi, (const FusedRare*)(h->fu.rare_dev + f.c * kRareSlots + f.slot), f.mask_prev);
 }
 template <int MODE>
 static void launch_fused_m(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, const hipEvent_t* ev) {
@@ -2242,7 +2341,7 @@ static int launch_fused(gsmpm_mpm* h, int mode, const FusedLaunch& f, hipStream_
 // the unfolded pipeline's launch: escape flag ep, slot buffer fslots
 static int launch_fused(gsmpm_mpm* h, int mode, int c, bool bin, bool use_box, uint32_t mask, float dt, int ep,
                         hipStream_t st, const hipEvent_t* ev) {
-  const FusedLaunch f{c, bin ? 1 : 0, use_box ? 1 : 0, ep, mask, mask, dt, h->fslots};
+  const FusedLaunch f{c, bin ? 1 : 0, use_box ? 1 : 0, ep, mask, mask, dt, h->fu.slots};
   return launch_fused(h, mode, f, st, ev);
 }
 
@@ -2256,7 +2355,7 @@ struct GridBufs {
   int* esc_clear;
 };
 static GridBufs grid_bufs(gsmpm_mpm* h, int wp, int ep) {
-  return GridBufs{h->fslots, h->ftbox[wp], h->gacc, h->fesc + ep, h->fesc + (ep ^ 1)};
+  return GridBufs{h->fu.slots, h->fu.tbox[wp], h->gacc, h->fu.esc + ep, h->fu.esc + (ep ^ 1)};
 }
 // after FOLD launch r (the re-binning one): its windows, boxes and escapes; the
 // rotation clears the flags, so the grid's own clear goes to a scratch word
@@ -2323,15 +2422,15 @@ static int launch_substeps_f(gsmpm_mpm* h, float dt, int nsub, const uint32_t* b
     const uint32_t mask_prev = s > 0 ? (bc ? bc[s - 1] : 0xffffffffu) : 0u;
     hipEvent_t* e8 = ev ? ev + 8 * s : nullptr;
     if (bin && !zeroed) {
-      GSMPM_HIP(hipMemsetAsync(h->fcount[bp ^ 1], 0, sizeof(int) * (h->ftl.ntiles + 1), st));
-      GSMPM_HIP(hipMemsetAsync(h->ftflag[bp ^ 1], 0, sizeof(int) * h->ftl.ntiles, st));
+      GSMPM_HIP(hipMemsetAsync(h->fu.b[bp ^ 1].count, 0, sizeof(int) * (h->ftl.ntiles + 1), st));
+      GSMPM_HIP(hipMemsetAsync(h->fu.b[bp ^ 1].tflag, 0, sizeof(int) * h->ftl.ntiles, st));
     }
-    if (mode == 1 && !h->slab && h->vmax_dev) GSMPM_HIP(hipMemsetAsync(h->vmax_dev, 0, sizeof(unsigned), st));
+    if (mode == 1 && !h->slab && h->fu.vmax_dev) GSMPM_HIP(hipMemsetAsync(h->fu.vmax_dev, 0, sizeof(unsigned), st));
     // FOLD: the launch before a re-binning one zeroes its counts (no grid launch between them)
     const bool zero_next = fold && !bin && s < nsub && bin_at(s + 1);
     const bool fl = fold && boxed && (mode & 1);
     const FusedLaunch f{bp, bin ? 1 : (zero_next ? 2 : 0), boxed ? 1 : 0, fold ? 2 + s % kFoldPhases : ep,
-                        mask, mask_prev, dt, fold ? fold_slots(h, s) : h->fslots};
+                        mask, mask_prev, dt, fold ? fold_slots(h, s) : h->fu.slots};
     int rc = launch_fused(h, fl ? mode + 4 : mode, f, st, e8);
     if (rc) return rc;
     if (zero_next) zeroed = true;
@@ -2347,8 +2446,8 @@ static int launch_substeps_f(gsmpm_mpm* h, float dt, int nsub, const uint32_t* b
       const bool next_bin = bin_at(s + 1);
       int *zc = nullptr, *zf = nullptr;
       if (next_bin && wp == bp) {  // this grid launch does not read parity bp ^ 1
-        zc = h->fcount[bp ^ 1];
-        zf = h->ftflag[bp ^ 1];
+        zc = h->fu.b[bp ^ 1].count;
+        zf = h->fu.b[bp ^ 1].tflag;
         zeroed = true;
       }
       rc = h->slab ? slab_grid_phase(h, wp, dt, mask, ep, zc, zf, st, xp)
@@ -2360,7 +2459,7 @@ static int launch_substeps_f(gsmpm_mpm* h, float dt, int nsub, const uint32_t* b
     }
   }
   if (fold) {  // escape accumulators the call's last launches left dirty, and the rotation's flags
-    hipLaunchKernelGGL(k_fold_tail, dim3(1), dim3(1024), 0, st, h->fesc + 2, h->gacc_f[0], h->gacc_f[1], h->gacc_f[2],
+    hipLaunchKernelGGL(k_fold_tail, dim3(1), dim3(1024), 0, st, h->fu.esc + 2, h->gacc, h->fo.gacc[0], h->fo.gacc[1],
                        h->g.ng);
     GSMPM_LAUNCH_CHECK();
   }
@@ -2418,7 +2517,7 @@ static int enter_mixed(gsmpm_mpm* h, const char* who, bool fill, hipStream_t st)
     set_error(std::string(who) + ": particles not set (gsmpm_mpm_set_particles resets the ids)");
     return GSMPM_ESTATE;
   }
-  if (!h->mat_ids) GSMPM_HIP(hipMalloc(&h->mat_ids, sizeof(float) * (size_t)h->np));
+  if (!h->mat_ids) GSMPM_HIP(alloc(h, &h->mat_ids, (size_t)h->np, kMemCommon));
   if (h->mixed) return GSMPM_OK;
   if (fill) {
     hipLaunchKernelGGL(k_fill_f, dim3(div_up(h->n, 256)), dim3(256), 0, st, h->mat_ids, h->n, (float)h->prm.material);
@@ -2486,20 +2585,18 @@ static int resort(gsmpm_mpm* h, hipStream_t st) {
   const int n = h->n, np = h->np;
   const int nch = std::max(1, div_up(np, kLsdChunk));
   if (!h->planes_tmp) {
-    GSMPM_HIP(hipMalloc(&h->planes_tmp, sizeof(float) * (size_t)NPLANES * np));
-    GSMPM_HIP(hipMalloc(&h->orig_tmp, sizeof(int) * (size_t)np));
-    GSMPM_HIP(hipMalloc(&h->sort_keys, sizeof(uint32_t) * 2 * (size_t)np));
-    GSMPM_HIP(hipMalloc(&h->sort_idx, sizeof(int) * 2 * (size_t)np));
-    // digit histograms and their row prefixes [2][256][nch], digit totals [256]
-    GSMPM_HIP(hipMalloc(&h->sort_tmp, sizeof(unsigned) * (2 * 256 * (size_t)nch + 256)));
-    h->sort_tmp_bytes = sizeof(unsigned) * (2 * 256 * (size_t)nch + 256);
+    GSMPM_HIP(alloc(h, &h->planes_tmp, (size_t)NPLANES * np, kMemCommon));
+    GSMPM_HIP(alloc(h, &h->orig_tmp, (size_t)np, kMemCommon));
+    GSMPM_HIP(alloc(h, &h->sort_keys, 2 * (size_t)np, kMemCommon));
+    GSMPM_HIP(alloc(h, &h->sort_idx, 2 * (size_t)np, kMemCommon));
+    GSMPM_HIP(alloc(h, &h->sort_tmp, 2 * 256 * (size_t)nch + 256, kMemCommon));
   }
   const dim3 pb(div_up(n, 256));
   hipLaunchKernelGGL(k_morton, pb, dim3(256), 0, st, particles_of(h), h->g.inv_dx, h->sort_keys, h->sort_idx);
   GSMPM_LAUNCH_CHECK();
   if (n > 0) {
     const int nc = div_up(n, kLsdChunk);
-    unsigned* H = reinterpret_cast<unsigned*>(h->sort_tmp);
+    unsigned* H = h->sort_tmp;
     unsigned* Hs = H + 256 * (size_t)nc;
     unsigned* tot = H + 2 * 256 * (size_t)nch;
     unsigned* kb[2] = {h->sort_keys, h->sort_keys + np};
@@ -2532,14 +2629,14 @@ static int slab_body(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc, hipSt
                      const gsmpm_transport* xp);  // slab_host.inc
 
 static gsmpm_mpm::FState fstate_of(const gsmpm_mpm* h, int bp, int ep) {
-  return gsmpm_mpm::FState{bp,      ep,          h->planes, h->planes_alt, h->orig, h->orig_alt, h->cold,
+  return gsmpm_mpm::FState{bp,      ep,          h->planes, h->fu.planes_alt, h->orig, h->fu.orig_alt, h->cold,
                            h->cold_alt, h->gid, h->gid_alt, h->s_since, h->s_migrations};
 }
 static void set_fstate(gsmpm_mpm* h, const gsmpm_mpm::FState& f) {
   h->planes = f.planes;
-  h->planes_alt = f.planes_alt;
+  h->fu.planes_alt = f.planes_alt;
   h->orig = f.orig;
-  h->orig_alt = f.orig_alt;
+  h->fu.orig_alt = f.orig_alt;
   h->cold = f.cold;
   h->cold_alt = f.cold_alt;
   h->gid = f.gid;
@@ -2574,7 +2671,7 @@ static int graph_substeps(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc, 
   key.push_back((uint32_t)h->rebin_interval);
   key.push_back(fold_on(h) ? 1u : 0u);
   key.push_back((uint32_t)h->rebin_m);
-  key.push_back(h->planes_alt && h->planes > h->planes_alt ? 1u : 0u);  // which particle buffer is current
+  key.push_back(h->fu.planes_alt && h->planes > h->fu.planes_alt ? 1u : 0u);  // which particle buffer is current
   key.push_back(xp ? (uint32_t)(((uintptr_t)xp->comm >> 4) ^ (uint32_t)xp->kind) : 0u);
   if (h->slab) {  // where the migrations fall, and the buffers they swap (rects / capacity changes drop graphs)
     key.push_back((uint32_t)(h->s_since % h->s_interval));
@@ -2704,40 +2801,22 @@ int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
   h->rebin_interval = h->mat_kernel == 0 ? kRebinStressFree : kRebinStress;
   const size_t nn = (size_t)h->g.ng * h->g.ng * h->g.ng;
   auto fail = [&](hipError_t e, const char* what) {
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    set_error(std::string("gsmpm_mpm_create: ") + what + ": " + hipGetErrorString(e));
     gsmpm_mpm_destroy(h);
     return GSMPM_EHIP;
   };
   hipError_t e;
-  if ((e = hipMalloc(&h->planes, sizeof(float) * (size_t)NPLANES * h->np)) != hipSuccess) return fail(e, "hipMalloc planes");
-  if ((e = hipMalloc(&h->cold, sizeof(float) * (size_t)NCOLD * h->np)) != hipSuccess) return fail(e, "hipMalloc planes");
-  if ((e = hipMemset(h->cold, 0, sizeof(float) * (size_t)NCOLD * h->np)) != hipSuccess) return fail(e, "hipMemset");
-  if ((e = hipMalloc(&h->orig, sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc orig");
-  if ((e = hipMalloc(&h->gacc, sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMalloc grid acc");
-  if ((e = hipMalloc(&h->gvel, sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMalloc grid vel");
+#define GSMPM_TRY(call, what) \
+  if ((e = (call)) != hipSuccess) return fail(e, what)
+  GSMPM_TRY(alloc(h, &h->planes, (size_t)NPLANES * h->np, kMemCommon, kFillZero), "planes");
+  GSMPM_TRY(alloc(h, &h->cold, (size_t)NCOLD * h->np, kMemCommon, kFillZero), "planes");
+  GSMPM_TRY(alloc(h, &h->orig, (size_t)h->np, kMemCommon), "orig");
+  GSMPM_TRY(alloc(h, &h->gacc, nn, kMemCommon, kFillZero), "grid acc");
+  GSMPM_TRY(alloc(h, &h->gvel, nn, kMemCommon, kFillZero), "grid vel");
   h->tl.td = (h->g.ng + kTile - 1) / kTile;
   h->tl.ntiles = h->tl.td * h->tl.td * h->tl.td;
   // every chunk but the last of each tile is full: <= n/256 + occupied tiles
   h->tl.max_chunks = h->n / kChunk + std::min(h->tl.ntiles + 1, h->n) + 1;
-  // + one all-zero slot (index max_chunks) that k_grid reads for absent tiles
-  if ((e = hipMalloc(&h->slots, sizeof(float4) * (size_t)(h->tl.max_chunks + 1) * kWin)) != hipSuccess)
-    return fail(e, "hipMalloc chunk slots");
-  if ((e = hipMemset(h->slots + (size_t)h->tl.max_chunks * kWin, 0, sizeof(float4) * kWin)) != hipSuccess)
-    return fail(e, "hipMemset");
-  for (int c = 0; c < 2; ++c) {
-    const size_t E = (size_t)h->tl.ntiles + 1;
-    if ((e = hipMalloc(&h->count[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc count");
-    if ((e = hipMalloc(&h->cstart[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc cstart");
-    if ((e = hipMalloc(&h->cbase[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc cbase");
-    if ((e = hipMalloc(&h->chunk[c], sizeof(int4) * (size_t)h->tl.max_chunks)) != hipSuccess) return fail(e, "hipMalloc chunk");
-    if ((e = hipMalloc(&h->touched[c], sizeof(int) * (size_t)h->tl.ntiles)) != hipSuccess) return fail(e, "hipMalloc touched");
-    if ((e = hipMalloc(&h->tflag[c], sizeof(int) * (size_t)h->tl.ntiles)) != hipSuccess) return fail(e, "hipMalloc tflag");
-    if ((e = hipMemset(h->tflag[c], 0, sizeof(int) * (size_t)h->tl.ntiles)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMalloc(&h->nchunk[c], sizeof(int) * 2)) != hipSuccess) return fail(e, "hipMalloc nchunk");
-    if ((e = hipMalloc(&h->list[c], sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc list");
-    if ((e = hipMemset(h->count[c], 0, sizeof(int) * E)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMemset(h->nchunk[c], 0, sizeof(int) * 2)) != hipSuccess) return fail(e, "hipMemset");
-  }
   // fused pipeline: 8 x 8 x 7-cell tiles (fused.h)
   h->fused = !(prm->flags & (GSMPM_FLAG_PHASED | GSMPM_FLAG_KEEP_GRID));
   if (const char* lb = std::getenv("GSMPM_LANE_BALANCE")) h->lane_balance = lb[0] != '0';
@@ -2778,106 +2857,57 @@ int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
   // ld_slot): a rank whose slot array would pass 4 GiB (~40M particles) runs
   // the per-phase pipeline instead
   if (h->fused && sizeof(float4) * (size_t)(h->ftl.max_chunks + 1) * kFWin > 0xffffffffull) h->fused = false;
-  if (h->fused) {
-    const size_t E = (size_t)h->ftl.ntiles + 1;
-    if ((e = hipMalloc(&h->fslots, sizeof(float4) * (size_t)(h->ftl.max_chunks + 1) * kFWin)) != hipSuccess)
-      return fail(e, "hipMalloc fused slots");
-    if ((e = hipMemset(h->fslots + (size_t)h->ftl.max_chunks * kFWin, 0, sizeof(float4) * kFWin)) != hipSuccess)
-      return fail(e, "hipMemset");
+  if (const char* fo = std::getenv("GSMPM_FOLD")) h->fold = h->fused && fo[0] != '0';
+  if (const char* ra = std::getenv("GSMPM_REBIN_AUTO")) h->rebin_auto = h->fused && ra[0] != '0';
+  if (!h->fused) {
+    GSMPM_TRY(alloc(h, &h->ph.slots, (size_t)(h->tl.max_chunks + 1) * kWin, kMemPhased, kFillZero,
+                    (size_t)h->tl.max_chunks * kWin),
+              "chunk slots");
+    for (BinLists& b : h->ph.b)
+      GSMPM_TRY(alloc_bin_lists(h, b, h->tl.ntiles, h->tl.max_chunks, kMemPhased), "bin lists");
+  } else {
+    FusedBufs& f = h->fu;
+    const size_t nt = (size_t)h->ftl.ntiles, mc = (size_t)h->ftl.max_chunks;
+    GSMPM_TRY(alloc(h, &f.slots, (mc + 1) * kFWin, kMemFused, kFillZero, mc * kFWin), "fused slots");
     for (int c = 0; c < 2; ++c) {
-      if ((e = hipMalloc(&h->fcount[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc count");
-      if ((e = hipMalloc(&h->fcstart[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc cstart");
-      if ((e = hipMalloc(&h->fcbase[c], sizeof(int) * E)) != hipSuccess) return fail(e, "hipMalloc cbase");
-      if ((e = hipMalloc(&h->fchunk[c], sizeof(int4) * (size_t)h->ftl.max_chunks)) != hipSuccess)
-        return fail(e, "hipMalloc chunk");
-      if ((e = hipMalloc(&h->ftouched[c], sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc touched");
-      // entries past the live count are never used, but a read of one must see a valid tile (round 3's
-      // uncommitted three-tiles-per-workgroup k_grid_f read past the count: hipErrorIllegalAddress)
-      if ((e = hipMemset(h->ftouched[c], 0, sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMemset touched");
-      if ((e = hipMalloc(&h->ftflag[c], sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc tflag");
-      if ((e = hipMalloc(&h->fnchunk[c], sizeof(int) * 2)) != hipSuccess) return fail(e, "hipMalloc nchunk");
-      if ((e = hipMalloc(&h->flist[c], sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc list");
-      if ((e = hipMalloc(&h->fcbox[c], sizeof(int) * (size_t)h->ftl.max_chunks)) != hipSuccess)
-        return fail(e, "hipMalloc boxes");
-      if ((e = hipMalloc(&h->fpchunk[c], sizeof(int4) * (size_t)h->ftl.max_chunks)) != hipSuccess ||
-          (e = hipMemset(h->fpchunk[c], 0, sizeof(int4) * (size_t)h->ftl.max_chunks)) != hipSuccess)
-        return fail(e, "hipMalloc ordered chunks");
-      if ((e = hipMalloc(&h->ftbox[c], sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc boxes");
-      if ((e = hipMalloc(&h->frcov[c], sizeof(int2) * kRecStride * (size_t)h->ftl.ntiles)) != hipSuccess ||
-          (e = hipMemset(h->frcov[c], 0, sizeof(int2) * kRecStride * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc cover records");
-      if ((e = hipMalloc(&h->frbox[c], sizeof(int) * kRecStride * (size_t)h->ftl.ntiles)) != hipSuccess ||
-          (e = hipMemset(h->frbox[c], 0, sizeof(int) * kRecStride * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc cover boxes");
-      if ((e = hipMalloc(&h->ftpos[c], sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess ||
-          (e = hipMemset(h->ftpos[c], 0xff, sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc touched positions");
-      if ((e = hipMalloc(&h->fperm[c], (size_t)h->ftl.max_chunks * 256)) != hipSuccess)
-        return fail(e, "hipMalloc lane balance");
-      if ((e = hipMemset(h->fperm[c], 0, (size_t)h->ftl.max_chunks * 256)) != hipSuccess) return fail(e, "hipMemset");
-      if ((e = hipMemset(h->fcount[c], 0, sizeof(int) * E)) != hipSuccess) return fail(e, "hipMemset");
-      if ((e = hipMemset(h->ftflag[c], 0, sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess) return fail(e, "hipMemset");
-      if ((e = hipMemset(h->fnchunk[c], 0, sizeof(int) * 2)) != hipSuccess) return fail(e, "hipMemset");
+      GSMPM_TRY(alloc_bin_lists(h, f.b[c], h->ftl.ntiles, h->ftl.max_chunks, kMemFused), "bin lists");
+      GSMPM_TRY(alloc(h, &f.cbox[c], mc, kMemFused), "boxes");
+      GSMPM_TRY(alloc(h, &f.pchunk[c], mc, kMemFused, kFillZero), "ordered chunks");
+      GSMPM_TRY(alloc(h, &f.tbox[c], nt, kMemFused), "boxes");
+      GSMPM_TRY(alloc(h, &f.rcov[c], kRecStride * nt, kMemFused, kFillZero), "cover records");
+      GSMPM_TRY(alloc(h, &f.rbox[c], kRecStride * nt, kMemFused, kFillZero), "cover boxes");
+      GSMPM_TRY(alloc(h, &f.tpos[c], nt, kMemFused, kFillOnes), "touched positions");
+      GSMPM_TRY(alloc(h, &f.perm[c], mc * 256, kMemFused, kFillZero), "lane balance");
     }
-    if ((e = hipMalloc(&h->planes_alt, sizeof(float) * (size_t)NPLANES * h->np)) != hipSuccess)
-      return fail(e, "hipMalloc planes");
-    if ((e = hipMemset(h->planes_alt, 0, sizeof(float) * (size_t)NPLANES * h->np)) != hipSuccess)
-      return fail(e, "hipMemset");
-    if ((e = hipMalloc(&h->orig_alt, sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc orig");
-    if ((e = hipMalloc(&h->fesc, sizeof(int) * (4 + kFoldPhases))) != hipSuccess) return fail(e, "hipMalloc escape flags");
-    if ((e = hipMemset(h->fesc, 0, sizeof(int) * (4 + kFoldPhases))) != hipSuccess) return fail(e, "hipMemset");
-    // FOLD (fused.h): the second slot and tile-box buffers, two more escape accumulators
-    if (const char* fo = std::getenv("GSMPM_FOLD")) h->fold = fo[0] != '0';
-    if ((e = hipMalloc(&h->fslots2, sizeof(float4) * (size_t)(h->ftl.max_chunks + 1) * kFWin)) != hipSuccess)
-      return fail(e, "hipMalloc fused slots");
-    if ((e = hipMemset(h->fslots2 + (size_t)h->ftl.max_chunks * kFWin, 0, sizeof(float4) * kFWin)) != hipSuccess)
-      return fail(e, "hipMemset");
-    h->gacc_f[0] = h->gacc;
-    for (int b = 1; b < 3; ++b) {
-      if ((e = hipMalloc(&h->gacc_f[b], sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMalloc grid acc");
-      if ((e = hipMemset(h->gacc_f[b], 0, sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMemset");
+    GSMPM_TRY(alloc(h, &f.planes_alt, (size_t)NPLANES * h->np, kMemFused, kFillZero), "planes");
+    GSMPM_TRY(alloc(h, &f.orig_alt, (size_t)h->np, kMemFused), "orig");
+    GSMPM_TRY(alloc(h, &f.esc, 4 + kFoldPhases, kMemFused, kFillZero), "escape flags");
+    GSMPM_TRY(alloc(h, &f.vmax_dev, 1, kMemFused, kFillZero), "vmax");
+    GSMPM_TRY(alloc_host(h, &f.vmax_host, 1), "pinned vmax");
+    *f.vmax_host = 0.f;
+    GSMPM_TRY(alloc(h, &f.rare_dev, 2 * kRareSlots, kMemFused, kFillZero), "rare args");
+    if (h->fold) {  // FOLD (fused.h): the second slot and tile-box buffers, two more escape accumulators
+      GSMPM_TRY(alloc(h, &h->fo.slots2, (mc + 1) * kFWin, kMemFold, kFillZero, mc * kFWin), "fused slots");
+      for (float4*& g : h->fo.gacc) GSMPM_TRY(alloc(h, &g, nn, kMemFold, kFillZero), "grid acc");
+      GSMPM_TRY(alloc(h, &h->fo.esc_nodes, 27 * (size_t)h->np, kMemFold), "escape nodes");
+      for (int*& t : h->fo.tbox2) GSMPM_TRY(alloc(h, &t, nt, kMemFold, kFillZero), "boxes");
     }
-    if ((e = hipMalloc(&h->fesc_nodes, sizeof(float4) * 27 * (size_t)h->np)) != hipSuccess)
-      return fail(e, "hipMalloc escape nodes");
-    if ((e = hipMalloc(&h->vmax_dev, sizeof(unsigned))) != hipSuccess ||
-        (e = hipMemset(h->vmax_dev, 0, sizeof(unsigned))) != hipSuccess)
-      return fail(e, "hipMalloc vmax");
-    if ((e = hipHostMalloc((void**)&h->vmax_host, sizeof(float), hipHostMallocDefault)) != hipSuccess)
-      return fail(e, "hipHostMalloc vmax");
-    *h->vmax_host = 0.f;
-    if (const char* ra = std::getenv("GSMPM_REBIN_AUTO")) h->rebin_auto = ra[0] != '0';
-    for (int c = 0; c < 2; ++c) {
-      if ((e = hipMalloc(&h->ftbox2[c], sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess)
-        return fail(e, "hipMalloc boxes");
-      if ((e = hipMemset(h->ftbox2[c], 0, sizeof(int) * (size_t)h->ftl.ntiles)) != hipSuccess) return fail(e, "hipMemset");
-    }
-    if ((e = hipMalloc(&h->frare_dev, sizeof(h->frare_host))) != hipSuccess) return fail(e, "hipMalloc rare args");
   }
   const int scan_tiles = std::max(h->tl.ntiles, h->ftl.ntiles) + 1;
-  if ((e = hipMalloc(&h->scan_part, sizeof(int4) * (size_t)div_up(scan_tiles, 1024))) != hipSuccess)
-    return fail(e, "hipMalloc scan partials");
-  if ((e = hipMalloc(&h->ptile, sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc ptile");
-  if ((e = hipMalloc(&h->pslot, sizeof(int) * (size_t)h->np)) != hipSuccess) return fail(e, "hipMalloc pslot");
-  if ((e = hipMalloc(&h->dev_bc, sizeof(BcTable))) != hipSuccess) return fail(e, "hipMalloc bc table");
-  if ((e = hipMemset(h->gacc, 0, sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMemset");
-  if ((e = hipMemset(h->gvel, 0, sizeof(float4) * nn)) != hipSuccess) return fail(e, "hipMemset");
-  if ((e = hipMemset(h->planes, 0, sizeof(float) * (size_t)NPLANES * h->np)) != hipSuccess) return fail(e, "hipMemset");
-  if ((e = hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+  GSMPM_TRY(alloc(h, &h->scan_part, (size_t)div_up(scan_tiles, 1024), kMemCommon), "scan partials");
+  GSMPM_TRY(alloc(h, &h->ptile, (size_t)h->np, kMemCommon), "ptile");
+  GSMPM_TRY(alloc(h, &h->pslot, (size_t)h->np, kMemCommon), "pslot");
+  GSMPM_TRY(alloc(h, &h->dev_bc, 1, kMemCommon), "bc table");
+  GSMPM_TRY(hipStreamCreateWithFlags(&h->cap, hipStreamNonBlocking), "hipStreamCreate");
   // the non-finite word: written by the kernels only when a position is NaN / Inf,
   // read by the host without a sync (step reports it at its next call)
-  if ((e = hipHostMalloc((void**)&h->nonfin_host, 64, hipHostMallocMapped)) != hipSuccess)
-    return fail(e, "hipHostMalloc");
+  GSMPM_TRY(alloc_host(h, &h->nonfin_host, 16, hipHostMallocMapped), "pinned non-finite word");
   *(volatile int*)h->nonfin_host = 0;
-  if ((e = hipHostGetDevicePointer((void**)&h->nonfin_dev, h->nonfin_host, 0)) != hipSuccess)
-    return fail(e, "hipHostGetDevicePointer");
+  GSMPM_TRY(hipHostGetDevicePointer((void**)&h->nonfin_dev, h->nonfin_host, 0), "hipHostGetDevicePointer");
   h->host_bc = BcTable{};
-  if ((e = hipMemcpy(h->dev_bc, &h->host_bc, sizeof(BcTable), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(e, "hipMemcpy bc");
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "init");
+  GSMPM_TRY(hipMemcpy(h->dev_bc, &h->host_bc, sizeof(BcTable), hipMemcpyHostToDevice), "hipMemcpy bc");
+  GSMPM_TRY(hipDeviceSynchronize(), "init");
+#undef GSMPM_TRY
   *out = h;
   return GSMPM_OK;
 }
@@ -2886,80 +2916,7 @@ int gsmpm_mpm_destroy(gsmpm_mpm* h) {
   if (!h) return GSMPM_OK;
   drop_graphs(h);
   if (h->cap) (void)hipStreamDestroy(h->cap);
-  (void)hipFree(h->planes);
-  (void)hipFree(h->cold);
-  (void)hipFree(h->orig);
-  (void)hipFree(h->mat_ids);
-  (void)hipFree(h->gacc);
-  (void)hipFree(h->gvel);
-  (void)hipFree(h->dev_bc);
-  (void)hipFree(h->slots);
-  for (int c = 0; c < 2; ++c) {
-    (void)hipFree(h->count[c]);
-    (void)hipFree(h->cstart[c]);
-    (void)hipFree(h->cbase[c]);
-    (void)hipFree(h->chunk[c]);
-    (void)hipFree(h->touched[c]);
-    (void)hipFree(h->tflag[c]);
-    (void)hipFree(h->nchunk[c]);
-    (void)hipFree(h->list[c]);
-  }
-  for (int c = 0; c < 2; ++c) {
-    (void)hipFree(h->fcount[c]);
-    (void)hipFree(h->fcstart[c]);
-    (void)hipFree(h->fcbase[c]);
-    (void)hipFree(h->fchunk[c]);
-    (void)hipFree(h->ftouched[c]);
-    (void)hipFree(h->ftflag[c]);
-    (void)hipFree(h->fnchunk[c]);
-    (void)hipFree(h->flist[c]);
-    (void)hipFree(h->fcbox[c]);
-    (void)hipFree(h->fpchunk[c]);
-    (void)hipFree(h->ftbox[c]);
-    (void)hipFree(h->fperm[c]);
-    (void)hipFree(h->frcov[c]);
-    (void)hipFree(h->frbox[c]);
-    (void)hipFree(h->ftpos[c]);
-  }
-  (void)hipFree(h->fslots);
-  (void)hipFree(h->fslots2);
-  (void)hipFree(h->gacc_f[1]);
-  (void)hipFree(h->gacc_f[2]);
-  for (int c = 0; c < 2; ++c) (void)hipFree(h->ftbox2[c]);
-  (void)hipFree(h->fesc_nodes);
-  (void)hipFree(h->vmax_dev);
-  if (h->vmax_host) (void)hipHostFree(h->vmax_host);
-  (void)hipFree(h->fesc);
-  (void)hipFree(h->frare_dev);
-  (void)hipFree(h->planes_alt);
-  (void)hipFree(h->orig_alt);
-  (void)hipFree(h->ptile);
-  (void)hipFree(h->scan_part);
-  (void)hipFree(h->pslot);
-  (void)hipFree(h->planes_tmp);
-  (void)hipFree(h->orig_tmp);
-  (void)hipFree(h->sort_keys);
-  (void)hipFree(h->sort_idx);
-  (void)hipFree(h->sort_tmp);
-  for (int w = 0; w < 2; ++w) {
-    (void)hipFree(h->sw.part[w]);
-    (void)hipFree(h->s_recv[w]);
-    (void)hipFree(h->mig_send[w]);
-    (void)hipFree(h->mig_recv[w]);
-  }
-  (void)hipFree(h->s_drift);
-  (void)hipFree(h->s_wdev);
-  (void)hipFree(h->d_n);
-  (void)hipFree(h->gid);
-  (void)hipFree(h->gid_alt);
-  (void)hipFree(h->cold_alt);
-  (void)hipFree(h->mig_bcnt);
-  (void)hipFree(h->mig_boff);
-  (void)hipFree(h->mig_tot);
-  (void)hipFree(h->s_rec);
-  if (h->s_rec_host) (void)hipHostFree(h->s_rec_host);
-  if (h->nonfin_host) (void)hipHostFree(h->nonfin_host);
-  if (h->x_host) (void)hipHostFree(h->x_host);
+  for (const MemRec& r : h->mem) free_rec(r);
   if (h->s_ev_pack) (void)hipEventDestroy(h->s_ev_pack);
   if (h->s_ev_x) (void)hipEventDestroy(h->s_ev_x);
   if (h->s_comm) (void)hipStreamDestroy(h->s_comm);
@@ -3009,10 +2966,10 @@ int gsmpm_mpm_set_particles(gsmpm_mpm* h, const float* x, const float* cov6, con
   const size_t nn = (size_t)h->g.ng * h->g.ng * h->g.ng;
   GSMPM_HIP(hipMemsetAsync(h->gacc, 0, nn * sizeof(float4), st));
   GSMPM_HIP(hipMemsetAsync(h->gvel, 0, nn * sizeof(float4), st));
-  if (h->fesc) {  // the fused pipeline's escape flags and the FOLD accumulators: a new state
-    GSMPM_HIP(hipMemsetAsync(h->fesc, 0, sizeof(int) * (4 + kFoldPhases), st));
-    for (int b = 1; b < 3; ++b) GSMPM_HIP(hipMemsetAsync(h->gacc_f[b], 0, nn * sizeof(float4), st));
-  }
+  // the fused pipeline's escape flags and the FOLD accumulators: a new state
+  if (h->fu.esc) GSMPM_HIP(hipMemsetAsync(h->fu.esc, 0, sizeof(int) * (4 + kFoldPhases), st));
+  for (float4* g : h->fo.gacc)
+    if (g) GSMPM_HIP(hipMemsetAsync(g, 0, nn * sizeof(float4), st));
   int rc = rebin(h, st);
   if (rc) return rc;
   GSMPM_HIP(hipStreamSynchronize(st));
@@ -3092,8 +3049,8 @@ namespace gsmpm {
 // time: the particles that leave their window take the escape path.
 static void choose_rebins(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc) {
   h->rebin_m = 0;
-  if (!h->rebin_auto || h->slab || !h->vmax_host || nsub < 2) return;
-  const float vprev = *(volatile float*)h->vmax_host;
+  if (!h->rebin_auto || h->slab || !h->fu.vmax_host || nsub < 2) return;
+  const float vprev = *(volatile float*)h->fu.vmax_host;
   const double g = std::sqrt(h->prm.gravity[0] * h->prm.gravity[0] + h->prm.gravity[1] * h->prm.gravity[1] +
                              h->prm.gravity[2] * h->prm.gravity[2]);
   const double v = (std::isfinite(vprev) ? (double)vprev : 0.0) + 2.0 * g * (double)nsub * dt;
@@ -3144,8 +3101,8 @@ int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, voi
     rc = graph_substeps(h, dt, nsub, bc, st, nullptr);
   }
   // the call's fastest velocity, for the next call's re-binnings (no sync)
-  if (!rc && use_fused(h) && h->vmax_host && h->rebin_auto)
-    GSMPM_HIP(hipMemcpyAsync(h->vmax_host, h->vmax_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  if (!rc && use_fused(h) && h->fu.vmax_host && h->rebin_auto)
+    GSMPM_HIP(hipMemcpyAsync(h->fu.vmax_host, h->fu.vmax_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   return rc;
 }
 
@@ -3190,7 +3147,7 @@ int gsmpm_mpm_escapes(gsmpm_mpm* h, int32_t clear, int64_t* out, void* stream) {
   if (!use_fused(h)) return GSMPM_OK;
   hipStream_t st = (hipStream_t)stream;
   unsigned v = 0;
-  unsigned* d = reinterpret_cast<unsigned*>(h->fesc + 3 + kFoldPhases);
+  unsigned* d = reinterpret_cast<unsigned*>(h->fu.esc + 3 + kFoldPhases);
   GSMPM_HIP(hipMemcpyAsync(&v, d, sizeof(v), hipMemcpyDeviceToHost, st));
   GSMPM_HIP(hipStreamSynchronize(st));
   if (clear) GSMPM_HIP(hipMemsetAsync(d, 0, sizeof(unsigned), st));
@@ -3203,13 +3160,24 @@ int gsmpm_mpm_rebin_state(gsmpm_mpm* h, int32_t* out3, float* vmax) {
   out3[0] = h->rebin_interval;
   out3[1] = h->rebin_auto ? 1 : 0;
   out3[2] = h->rebin_m;
-  if (vmax) *vmax = h->vmax_host ? *(volatile float*)h->vmax_host : 0.f;
+  if (vmax) *vmax = h->fu.vmax_host ? *(volatile float*)h->fu.vmax_host : 0.f;
   return GSMPM_OK;
 }
 
 int gsmpm_mpm_folded(gsmpm_mpm* h) {
   GSMPM_REQUIRE(h, "gsmpm_mpm_folded: null handle");
   return use_fused(h) && fold_on(h) ? 1 : 0;
+}
+
+int gsmpm_mpm_device_bytes(gsmpm_mpm* h, uint64_t* out4) {
+  GSMPM_REQUIRE(h && out4, "gsmpm_mpm_device_bytes: null argument");
+  for (int k = 0; k < 4; ++k) out4[k] = 0;
+  for (const MemRec& r : h->mem) {
+    if (r.group == kMemPinned) continue;
+    out4[0] += r.bytes;
+    if (r.group != kMemCommon) out4[r.group] += r.bytes;  // kMemPhased / kMemFused / kMemFold: 1..3
+  }
+  return GSMPM_OK;
 }
 
 int gsmpm_mpm_resort(gsmpm_mpm* h, int32_t interval, void* stream) {
@@ -3421,12 +3389,12 @@ static int time_kernels_f(gsmpm_mpm* h, float dt, uint32_t mask, int reps, float
   if (!rc) rc = launch_grid_f(h, c, dt, mask, ep, nullptr, nullptr, st, nullptr);
   if (!rc) rc = timed(0, [&]() { return launch_fused(h, 3, c, false, true, mask, dt, ep, st, nullptr); });
   if (!rc) {
-    GSMPM_HIP(hipMemsetAsync(h->fesc, 0, 2 * sizeof(int), st));  // time the touched-tile update
+    GSMPM_HIP(hipMemsetAsync(h->fu.esc, 0, 2 * sizeof(int), st));  // time the touched-tile update
     rc = timed(1, [&]() { return launch_grid_f(h, c, dt, mask, ep, nullptr, nullptr, st, nullptr); });
   }
   if (!rc) {
-    GSMPM_HIP(hipMemsetAsync(h->fcount[c ^ 1], 0, sizeof(int) * (h->ftl.ntiles + 1), st));
-    GSMPM_HIP(hipMemsetAsync(h->ftflag[c ^ 1], 0, sizeof(int) * h->ftl.ntiles, st));
+    GSMPM_HIP(hipMemsetAsync(h->fu.b[c ^ 1].count, 0, sizeof(int) * (h->ftl.ntiles + 1), st));
+    GSMPM_HIP(hipMemsetAsync(h->fu.b[c ^ 1].tflag, 0, sizeof(int) * h->ftl.ntiles, st));
     rc = launch_fused(h, 1, c, true, true, mask, dt, ep, st, nullptr);
     if (!rc) rc = timed(2, [&]() { return finish_binning_f(h, c ^ 1, st); });
   }
@@ -3434,7 +3402,7 @@ static int time_kernels_f(gsmpm_mpm* h, float dt, uint32_t mask, int reps, float
   (void)hipEventDestroy(e[1]);
   if (rc) return rc;
   GSMPM_HIP(hipMemcpyAsync(h->planes, h->planes_tmp, pbytes, hipMemcpyDeviceToDevice, st));
-  GSMPM_HIP(hipMemsetAsync(h->fesc, 0, 2 * sizeof(int), st));
+  GSMPM_HIP(hipMemsetAsync(h->fu.esc, 0, 2 * sizeof(int), st));
   GSMPM_HIP(hipMemsetAsync(h->gacc, 0, nn * sizeof(float4), st));
   return rebin(h, st);
 }
@@ -3447,7 +3415,7 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
   }
   hipStream_t st = (hipStream_t)stream;
   const size_t pbytes = sizeof(float) * (size_t)NPLANES * h->np;
-  if (!h->planes_tmp) GSMPM_HIP(hipMalloc(&h->planes_tmp, pbytes));
+  if (!h->planes_tmp) GSMPM_HIP(alloc(h, &h->planes_tmp, (size_t)NPLANES * h->np, kMemCommon));
   GSMPM_HIP(hipMemcpyAsync(h->planes_tmp, h->planes, pbytes, hipMemcpyDeviceToDevice, st));
   if (use_fused(h)) return time_kernels_f(h, dt, bc_active, reps, ms4, st, pbytes);
   const int c = h->cur_box, nx = c ^ 1;
@@ -3456,7 +3424,7 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
   GSMPM_HIP(hipEventCreate(&e[0]));
   GSMPM_HIP(hipEventCreate(&e[1]));
   auto grid = [&]() {
-    launch(nullptr, k_grid, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c), (const float4*)h->slots,
+    launch(nullptr, k_grid, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c), (const float4*)h->ph.slots,
            h->gacc, h->gvel, (const BcTable*)h->dev_bc, gs, bin_out(h, nx));
   };
   auto g2p = [&]() {
@@ -3505,9 +3473,9 @@ int gsmpm_mpm_debug_stats(gsmpm_mpm* h, int32_t* out8, void* stream) {
   const int ntiles = fz ? h->ftl.ntiles : h->tl.ntiles, par = fz ? h->fbpar : h->cur_box;
   std::vector<int> hc(ntiles + 1);
   int nch[2] = {0, 0};
-  GSMPM_HIP(hipMemcpyAsync(hc.data(), fz ? h->fcount[par] : h->count[par], sizeof(int) * hc.size(),
+  GSMPM_HIP(hipMemcpyAsync(hc.data(), bin_lists(h, par).count, sizeof(int) * hc.size(),
                            hipMemcpyDeviceToHost, st));
-  GSMPM_HIP(hipMemcpyAsync(nch, fz ? h->fnchunk[par] : h->nchunk[par], sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+  GSMPM_HIP(hipMemcpyAsync(nch, bin_lists(h, par).nchunk, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
   GSMPM_HIP(hipStreamSynchronize(st));
   int active = 0, mx = 0;
   long tot = 0;
@@ -3546,11 +3514,11 @@ int gsmpm_mpm_live_box(gsmpm_mpm* h, int32_t* box6, void* stream) {
   const bool fz = use_fused(h);
   const int c = fz ? h->fbpar : h->cur_box, td = h->tl.td;
   int nch[2] = {0, 0};
-  GSMPM_HIP(hipMemcpyAsync(nch, fz ? h->fnchunk[c] : h->nchunk[c], sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+  GSMPM_HIP(hipMemcpyAsync(nch, bin_lists(h, c).nchunk, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
   GSMPM_HIP(hipStreamSynchronize(st));
   std::vector<int> tl(nch[1]);
   if (nch[1] > 0) {
-    GSMPM_HIP(hipMemcpyAsync(tl.data(), fz ? h->ftouched[c] : h->touched[c], sizeof(int) * nch[1],
+    GSMPM_HIP(hipMemcpyAsync(tl.data(), bin_lists(h, c).touched, sizeof(int) * nch[1],
                              hipMemcpyDeviceToHost, st));
     GSMPM_HIP(hipStreamSynchronize(st));
   }

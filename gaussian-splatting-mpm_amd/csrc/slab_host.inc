@@ -113,13 +113,13 @@ static int xport_exchange(gsmpm_mpm* h, const gsmpm_transport* xp, hipStream_t s
   size_t tot = 0;
   for (int i = 0; i < n; ++i) tot += ((sb[i] + 255) & ~size_t(255)) + ((rb[i] + 255) & ~size_t(255));
   if (tot > h->x_host_cap) {
-    if (h->x_host) GSMPM_HIP(hipHostFree(h->x_host));
-    h->x_host = nullptr;
-    GSMPM_HIP(hipHostMalloc((void**)&h->x_host, tot + tot / 2 + 4096, hipHostMallocDefault));
+    release(h, &h->x_host);
+    h->x_host_cap = 0;
+    GSMPM_HIP(alloc_host(h, &h->x_host, tot + tot / 2 + 4096));
     h->x_host_cap = tot + tot / 2 + 4096;
   }
   std::vector<void*> hs(n), hr(n);
-  char* q = reinterpret_cast<char*>(h->x_host);
+  char* q = h->x_host;
   for (int i = 0; i < n; ++i) {
     hs[i] = q;
     q += (sb[i] + 255) & ~size_t(255);
@@ -203,13 +203,17 @@ static int slab_grid_phase(gsmpm_mpm* h, int wp, float dt, uint32_t mask, int ep
   return GSMPM_OK;
 }
 
-static int grow_dev(void** p, size_t& cap, size_t need, size_t unit) {
-  if (need <= cap) return GSMPM_OK;
-  const size_t ncap = need + need / 2 + 1024;
-  if (*p) GSMPM_HIP(hipFree(*p));
-  *p = nullptr;
-  GSMPM_HIP(hipMalloc(p, ncap * unit));
-  cap = ncap;
+// the migration payloads of `cap` leavers a way, zeroed (they only grow; the
+// caller drops the graphs, which bake their size and addresses)
+static int grow_mig(gsmpm_mpm* h, int cap) {
+  for (int w = 0; w < 2; ++w) {
+    if (!h->s_has[w]) continue;
+    release(h, &h->mig_send[w]);
+    release(h, &h->mig_recv[w]);
+    GSMPM_HIP(alloc(h, &h->mig_send[w], mig_payload_floats(cap), kMemCommon, kFillZero));
+    GSMPM_HIP(alloc(h, &h->mig_recv[w], mig_payload_floats(cap), kMemCommon, kFillZero));
+  }
+  h->mig_cap = cap;
   return GSMPM_OK;
 }
 
@@ -327,18 +331,8 @@ static int slab_rebalance(gsmpm_mpm* h) {
   int cap = std::max(256, h->mig_cap);
   while (cap < 2 * moved && cap < h->np) cap *= 2;
   if (cap > h->mig_cap) {
-    const size_t bytes = mig_payload_floats(cap) * sizeof(float);
-    for (int w = 0; w < 2; ++w) {
-      if (!h->s_has[w]) continue;
-      (void)hipFree(h->mig_send[w]);
-      (void)hipFree(h->mig_recv[w]);
-      h->mig_send[w] = h->mig_recv[w] = nullptr;
-      GSMPM_HIP(hipMalloc(&h->mig_send[w], bytes));
-      GSMPM_HIP(hipMalloc(&h->mig_recv[w], bytes));
-      GSMPM_HIP(hipMemset(h->mig_send[w], 0, bytes));
-      GSMPM_HIP(hipMemset(h->mig_recv[w], 0, bytes));
-    }
-    h->mig_cap = cap;
+    const int rc = grow_mig(h, cap);
+    if (rc) return rc;
   }
   h->s_bounds = nb;
   h->s_lo = nb[h->s_rank];
@@ -381,18 +375,8 @@ static int slab_check(gsmpm_mpm* h, hipStream_t st) {
   if (const char* mc = std::getenv("GSMPM_SLAB_MIG_CAP"))
     if (h->mig_cap == 0) cap = std::max(1, std::atoi(mc));
   if (world > 1 && cap > h->mig_cap) {
-    const size_t bytes = mig_payload_floats(cap) * sizeof(float);
-    for (int w = 0; w < 2; ++w) {
-      if (!h->s_has[w]) continue;
-      (void)hipFree(h->mig_send[w]);
-      (void)hipFree(h->mig_recv[w]);
-      h->mig_send[w] = h->mig_recv[w] = nullptr;
-      GSMPM_HIP(hipMalloc(&h->mig_send[w], bytes));
-      GSMPM_HIP(hipMalloc(&h->mig_recv[w], bytes));
-      GSMPM_HIP(hipMemset(h->mig_send[w], 0, bytes));
-      GSMPM_HIP(hipMemset(h->mig_recv[w], 0, bytes));
-    }
-    h->mig_cap = cap;
+    const int rc = grow_mig(h, cap);
+    if (rc) return rc;
     drop_graphs(h);  // the payload size and buffers are baked into them
   }
   for (int r = 0; r < world; ++r) {
@@ -531,7 +515,7 @@ static int slab_migrate(gsmpm_mpm* h, const gsmpm_transport* xp, hipStream_t st)
   hipLaunchKernelGGL(k_mig_count, dim3(nblk), dim3(256), 0, st, particles_of(h), mg, h->mig_bcnt);
   hipLaunchKernelGGL(k_mig_scan, dim3(1), dim3(1024), 0, st, nblk, (const int*)h->mig_bcnt, h->mig_boff, h->mig_tot,
                      ms);
-  const MigOut mo{h->planes_alt, h->cold_alt, h->gid_alt};
+  const MigOut mo{h->fu.planes_alt, h->cold_alt, h->gid_alt};
   hipLaunchKernelGGL(k_mig_scatter, dim3(nblk), dim3(256), 0, st, particles_of(h), (const int*)h->orig,
                      (const int*)h->gid, mg, (const int*)h->mig_boff, (const int*)h->mig_tot, mo, ms);
   GSMPM_LAUNCH_CHECK();
@@ -553,11 +537,11 @@ static int slab_migrate(gsmpm_mpm* h, const gsmpm_transport* xp, hipStream_t st)
   }
   const MigRecv mr{{h->s_has[0] ? h->mig_recv[0] : nullptr, h->s_has[1] ? h->mig_recv[1] : nullptr}, h->mig_cap};
   hipLaunchKernelGGL(k_mig_unpack, dim3(std::max(1, div_up(h->mig_cap, 256)), 2), dim3(256), 0, st, mr,
-                     (const int*)h->mig_tot, h->planes_alt, h->cold_alt, h->gid_alt, h->np, h->prm.n_particles);
+                     (const int*)h->mig_tot, h->fu.planes_alt, h->cold_alt, h->gid_alt, h->np, h->prm.n_particles);
   hipLaunchKernelGGL(k_mig_finish, dim3(nblk), dim3(256), 0, st, mr, (const int*)h->mig_tot, h->prm.n_particles,
                      h->d_n, h->orig, h->s_drift);
   GSMPM_LAUNCH_CHECK();
-  std::swap(h->planes, h->planes_alt);
+  std::swap(h->planes, h->fu.planes_alt);
   std::swap(h->cold, h->cold_alt);
   std::swap(h->gid, h->gid_alt);
   h->s_migrations += 1;
@@ -662,38 +646,32 @@ int gsmpm_mpm_slab_init(gsmpm_mpm* h, int32_t rank, int32_t world, int32_t lo, i
     sw.y0[w] = sw.z0[w] = 0;
     sw.ny[w] = sw.nz[w] = ng;
   }
-  const size_t wbytes = sizeof(float4) * (size_t)W * ng * ng;
+  const size_t wcount = (size_t)W * ng * ng;
   for (int w = 0; w < 2; ++w) {
     if (!sw.on[w]) continue;
-    GSMPM_HIP(hipMalloc(&sw.part[w], wbytes));
-    GSMPM_HIP(hipMemset(sw.part[w], 0, wbytes));
-    GSMPM_HIP(hipMalloc(&h->s_recv[w], wbytes));
-    GSMPM_HIP(hipMemset(h->s_recv[w], 0, wbytes));
+    GSMPM_HIP(alloc(h, &sw.part[w], wcount, kMemCommon, kFillZero));
+    GSMPM_HIP(alloc(h, &h->s_recv[w], wcount, kMemCommon, kFillZero));
   }
   h->sw = sw;
   const size_t np = (size_t)h->np, nblk = (size_t)std::max(1, div_up(h->np, 256));
-  GSMPM_HIP(hipMalloc(&h->d_n, sizeof(int)));
-  GSMPM_HIP(hipMemset(h->d_n, 0, sizeof(int)));
-  GSMPM_HIP(hipMalloc(&h->s_drift, kSlabFlags * sizeof(int)));
-  GSMPM_HIP(hipMemset(h->s_drift, 0, kSlabFlags * sizeof(int)));
+  GSMPM_HIP(alloc(h, &h->d_n, 1, kMemCommon, kFillZero));
+  GSMPM_HIP(alloc(h, &h->s_drift, kSlabFlags, kMemCommon, kFillZero));
   if (!h->s_wdev) {
-    GSMPM_HIP(hipMalloc(&h->s_wdev, sizeof(float)));
+    GSMPM_HIP(alloc(h, &h->s_wdev, 1, kMemCommon));
     GSMPM_HIP(hipMemcpy(h->s_wdev, &h->s_weight, sizeof(float), hipMemcpyHostToDevice));
   }
   h->sw.oob = h->s_drift + SF_OOB;
   h->s_rect_set = false;
   h->s_synced = false;
-  GSMPM_HIP(hipMalloc(&h->gid, sizeof(int) * np));
-  GSMPM_HIP(hipMalloc(&h->gid_alt, sizeof(int) * np));
-  GSMPM_HIP(hipMalloc(&h->cold_alt, sizeof(float) * (size_t)NCOLD * np));
-  GSMPM_HIP(hipMemset(h->cold_alt, 0, sizeof(float) * (size_t)NCOLD * np));
-  GSMPM_HIP(hipMalloc(&h->mig_bcnt, sizeof(int) * 3 * nblk));
-  GSMPM_HIP(hipMalloc(&h->mig_boff, sizeof(int) * 3 * nblk));
-  GSMPM_HIP(hipMalloc(&h->mig_tot, sizeof(int) * 8));
+  GSMPM_HIP(alloc(h, &h->gid, np, kMemCommon));
+  GSMPM_HIP(alloc(h, &h->gid_alt, np, kMemCommon));
+  GSMPM_HIP(alloc(h, &h->cold_alt, (size_t)NCOLD * np, kMemCommon, kFillZero));
+  GSMPM_HIP(alloc(h, &h->mig_bcnt, 3 * nblk, kMemCommon));
+  GSMPM_HIP(alloc(h, &h->mig_boff, 3 * nblk, kMemCommon));
+  GSMPM_HIP(alloc(h, &h->mig_tot, 8, kMemCommon));
   GSMPM_REQUIRE(ng <= kRecMaxNg, "gsmpm_mpm_slab_init: n_grid above 4096");
-  GSMPM_HIP(hipMalloc(&h->s_rec, sizeof(int) * rec_ints_of(ng) * (size_t)world));
-  GSMPM_HIP(hipHostMalloc((void**)&h->s_rec_host, sizeof(int) * rec_ints_of(ng) * (size_t)world,
-                          hipHostMallocDefault));
+  GSMPM_HIP(alloc(h, &h->s_rec, rec_ints_of(ng) * (size_t)world, kMemCommon));
+  GSMPM_HIP(alloc_host(h, &h->s_rec_host, rec_ints_of(ng) * (size_t)world));
   GSMPM_HIP(hipStreamCreateWithFlags(&h->s_comm, hipStreamNonBlocking));
   GSMPM_HIP(hipEventCreateWithFlags(&h->s_ev_pack, hipEventDisableTiming));
   GSMPM_HIP(hipEventCreateWithFlags(&h->s_ev_x, hipEventDisableTiming));

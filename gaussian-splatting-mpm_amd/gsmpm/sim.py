@@ -243,6 +243,13 @@ class Simulator:
         launch (gsmpm_mpm_folded; one launch per substep)."""
         return bool(check(LIB.gsmpm_mpm_folded(self._h), "gsmpm_mpm_folded"))
 
+    def device_bytes(self) -> dict:
+        """Device memory the handle holds, in requested bytes (gsmpm_mpm_device_bytes):
+        'total' and its 'phased', 'fused' and 'fold' parts."""
+        out = (ctypes.c_uint64 * 4)()
+        check(LIB.gsmpm_mpm_device_bytes(self._h, out), "gsmpm_mpm_device_bytes")
+        return dict(zip(("total", "phased", "fused", "fold"), (int(v) for v in out)))
+
     def escapes(self, clear: bool = False) -> int:
         """Particle scatters that left their chunk window since set_particles or
         the last clear (gsmpm_mpm_escapes; syncs the stream)."""

@@ -234,8 +234,18 @@ int gsmpm_mpm_pipeline(gsmpm_mpm* h);
  * re-binning): GSMPM_FOLD=1 in the environment at create, off by default
  * (measured slower); 0 otherwise (the default, the per-phase
  * pipeline, slabs).  The grid update it folds is utils.py:177-183 +
- * solver.py:41-46; without escapes the results are bit-identical either way. */
+ * solver.py:41-46; without escapes the results are bit-identical either way.
+ * The FOLD buffers exist only on a handle created with GSMPM_FOLD=1: one for
+ * which this returns 1, or a slab made from one. */
 int gsmpm_mpm_folded(gsmpm_mpm* h);
+/* Device memory the handle holds now, in bytes: out4 = {total, per-phase
+ * pipeline's buffers, fused pipeline's buffers, FOLD buffers} (the last three
+ * are parts of the total; a handle has the buffers of the pipeline it runs
+ * only).  The figures are the sizes requested from hipMalloc; the driver may
+ * round each allocation up.  Pinned host memory is not counted.  Buffers
+ * allocated on first use (per-particle material ids, the re-sort's and the
+ * slab's) count once they exist.  Makes no HIP call.  No reference counterpart. */
+int gsmpm_mpm_device_bytes(gsmpm_mpm* h, uint64_t* out4);
 /* Fused pipeline diagnostics: the particle scatters since set_particles (or
  * the last clear) that left their chunk's window -- they took the global
  * float-atomic path, and the next grid update evaluates every node they may

@@ -86,6 +86,10 @@ def test_null_arguments_fail_loudly_without_a_gpu():
     assert _lib.LIB.gsmpm_mpm_step(None, ctypes.c_float(1e-4), 1, None, None) < 0
     assert _lib.LIB.gsmpm_mpm_field_width(_lib.FIELD["C"]) == 9
     assert _lib.LIB.gsmpm_mpm_field_width(99) < 0
+    buf = (ctypes.c_uint64 * 4)()
+    assert _lib.LIB.gsmpm_mpm_device_bytes(None, buf) == _lib.GSMPM_EINVAL
+    assert "gsmpm_mpm_device_bytes: null argument" in _lib.last_error()
+    assert _lib.LIB.gsmpm_mpm_device_bytes(None, None) == _lib.GSMPM_EINVAL
 
 
 # ------------------------------------------------------------- arguments --
