@@ -28,7 +28,8 @@
 // accumulate each chunk of <= 256 same-tile particles into a 10^3-node LDS
 // window as 64-bit fixed point (ds_add_u64: ~9 cycles per wave-instruction on
 // gfx950 against ~192 for ds_add_f32, tools/ubench/lds_atomics.hip; per-chunk,
-// per-channel power-of-two scales chosen from a bound on the contributions),
+// per-channel power-of-two scales chosen from a bound on the contributions,
+// with a 32-bit word for what falls below the 64-bit one's last bit),
 // and store the window to the chunk's slot with plain stores.  The grid
 // kernels then sum the chunk windows covering each node in a fixed order; no
 // global float atomic is used (scattered ones run ~17x below the atomic byte
@@ -302,18 +303,41 @@ __device__ __forceinline__ void stvk_stress(const float F[9], float mu, float la
 }
 
 // ------------------------------------------------ fixed-point LDS windows ---
-// v * 2^S rounded to an integer as two's complement int64 (|v * 2^S| < 2^51):
-// adding 1.5 * 2^52 in f64 leaves the integer in the low mantissa bits.
-__device__ __forceinline__ unsigned long long to_fixed(float v, double scale) {
-  const double d = __builtin_fma((double)v, scale, 6755399441055744.0);
-  return (unsigned long long)__double_as_longlong(d) - 0x4338000000000000ull;
+// v * 2^S in two words (|v * 2^S| < 2^51).  hi: rounded to an integer as
+// two's complement int64 (adding 1.5 * 2^52 in f64 leaves the integer in the
+// low mantissa bits).  lo: what that rounding left, (v * 2^S - hi) in units of
+// 2^-22, |lo| <= 2^21: the low 32 bits of the same rounding of v * 2^(S + 22)
+// minus those of hi * 2^22; 0 when |v * 2^S| >= 2^24 (24 mantissa bits: an
+// integer already).  The chunk's scale comes from its largest contribution; a
+// node that only sees near-zero spline weights sums contributions 2^-40 of
+// that and smaller (a node mass may be 1e-15 of a particle's and still counts,
+// utils.py:180), and hi alone would leave it a few bits.  No branch: a
+// workgroup runs one wave per SIMD, and 108 of them per lane would each expose
+// their latency.
+struct Scale {
+  double s, s22;   // 2^S, 2^(S + 22)
+  float lo_below;  // 2^(24 - S)
+};
+__device__ __forceinline__ Scale make_scale(int S) { return {ldexp(1.0, S), ldexp(1.0, S + 22), (float)ldexp(1.0, 24 - S)}; }
+__device__ __forceinline__ void lds_add(unsigned long long* hi, int* lo, int l, float v, const Scale& sc) {
+  const double d = __builtin_fma((double)v, sc.s, 6755399441055744.0);
+  const unsigned long long h = (unsigned long long)__double_as_longlong(d) - 0x4338000000000000ull;
+  __hip_atomic_fetch_add(hi + l, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  const double t = __builtin_fma((double)v, sc.s22, 6755399441055744.0);
+  const int q = (int)((unsigned)__double_as_longlong(t) - ((unsigned)h << 22));
+  __hip_atomic_fetch_add(lo + l, fabsf(v) < sc.lo_below ? q : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-__device__ __forceinline__ void lds_add(unsigned long long* a, unsigned long long v) {
-  __hip_atomic_fetch_add(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+// Zero a window's hi and lo planes, 16 bytes a store.
+template <int NCH>
+__device__ __forceinline__ void zero_window(unsigned long long* hi, int* lo) {
+  int4* const a = reinterpret_cast<int4*>(hi);
+  int4* const b = reinterpret_cast<int4*>(lo);
+  for (int l = threadIdx.x; l < NCH * kWin3 / 2; l += kChunk) a[l] = make_int4(0, 0, 0, 0);
+  for (int l = threadIdx.x; l < NCH * kWin3 / 4; l += kChunk) b[l] = make_int4(0, 0, 0, 0);
 }
 // Workgroup max of a per-lane bound on |contribution| -> scale 2^S with every
-// scaled contribution below 2^50 (to_fixed needs < 2^51); a node sums <= 256
-// of them, < 2^58: no int64 overflow.  Resolution: 2^-50 of the chunk's bound.
+// scaled contribution below 2^50 (the rounding above needs < 2^51); a node sums <= 256
+// of them, < 2^58 (lo: < 2^29): no overflow.  Resolution: 2^-72 of the chunk's bound.
 __device__ __forceinline__ int chunk_exponent(float bound, float* s_max, int slot) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o));
@@ -326,13 +350,14 @@ __device__ __forceinline__ int chunk_exponent(float bound, float* s_max, int slo
   return b > 0.f ? 50 - e : 0;
 }
 
-// Window (nch u64 planes) -> the chunk's slot: float4 per node, channel c -> .x/.y/.z/.w
-__device__ __forceinline__ void store_window(const View& V, const unsigned long long* win, int nch, const int* S,
-                                             int chunk) {
+// Window (nch hi and lo planes) -> the chunk's slot: float4 per node, channel c -> .x/.y/.z/.w
+__device__ __forceinline__ void store_window(const View& V, const unsigned long long* win, const int* lo, int nch,
+                                             const int* S, int chunk) {
   float4* dst = V.slots + (size_t)chunk * kWin3;
   for (int l = threadIdx.x; l < kWin3; l += kChunk) {
     float c[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int ch = 0; ch < nch; ++ch) c[ch] = (float)ldexp((double)(long long)win[ch * kWin3 + l], -S[ch]);
+    for (int ch = 0; ch < nch; ++ch)
+      c[ch] = (float)ldexp((double)(long long)win[ch * kWin3 + l] + (double)lo[ch * kWin3 + l] * (1.0 / 4194304.0), -S[ch]);
     // write-through: the grid kernels read the slots from other XCDs (common.h)
     wt_store4(dst + l, make_float4(c[0], c[1], c[2], c[3]));
   }
@@ -344,12 +369,13 @@ __device__ __forceinline__ void store_window(const View& V, const unsigned long 
 // Slot layout: (m v_in x, y, z, m).
 template <bool RECOMPUTE>
 __global__ __launch_bounds__(kChunk) void k_p2g(View V, int s, float dt) {
-  __shared__ unsigned long long win[4 * kWin3];
+  __shared__ __align__(16) unsigned long long win[4 * kWin3];
+  __shared__ __align__(16) int wlo[4 * kWin3];
   __shared__ float s_max[8];
   const int c = blockIdx.x;
   if (c >= V.nchunks[s]) return;
   const int4 rec = V.chunks[(size_t)s * V.max_chunks + c];
-  for (int l = threadIdx.x; l < 4 * kWin3; l += kChunk) win[l] = 0ull;
+  zero_window<4>(win, wlo);
   const int tz = rec.x % V.nta, ty = (rec.x / V.nta) % V.nta, tx = rec.x / (V.nta * V.nta);
   const int ox = tx * kTile, oy = ty * kTile, oz = tz * kTile;
   const bool on = (int)threadIdx.x < rec.z;
@@ -384,7 +410,7 @@ __global__ __launch_bounds__(kChunk) void k_p2g(View V, int s, float dt) {
   S[3] = chunk_exponent(bm, s_max, 0);
   S[0] = S[1] = S[2] = chunk_exponent(bv, s_max, 1);  // its barrier also orders the zeroing
   if (on) {
-    const double sc_v = ldexp(1.0, S[0]), sc_m = ldexp(1.0, S[3]);
+    const Scale sc_v = make_scale(S[0]), sc_m = make_scale(S[3]);
     int base[3];
     float fx[3], w[3][3], dw[3][3];
     bsp(x, V.inv_dx, base, fx, w, dw);
@@ -404,13 +430,13 @@ __global__ __launch_bounds__(kChunk) void k_p2g(View V, int s, float dt) {
           for (int r = 0; r < 3; ++r) {
             const float cd = Cm[r * 3 + 0] * dpos[0] + Cm[r * 3 + 1] * dpos[1] + Cm[r * 3 + 2] * dpos[2];
             const float ef = -vol * (sg[r * 3 + 0] * gw[0] + sg[r * 3 + 1] * gw[1] + sg[r * 3 + 2] * gw[2]);
-            lds_add(&win[r * kWin3 + l], to_fixed(weight * m * (vv[r] + cd) + dt * ef, sc_v));
+            lds_add(win, wlo, r * kWin3 + l, weight * m * (vv[r] + cd) + dt * ef, sc_v);
           }
-          lds_add(&win[3 * kWin3 + l], to_fixed(weight * m, sc_m));
+          lds_add(win, wlo, 3 * kWin3 + l, weight * m, sc_m);
         }
   }
   __syncthreads();
-  store_window(V, win, 4, S, c);
+  store_window(V, win, wlo, 4, S, c);
 }
 
 // Grid kernels run one 512-thread workgroup per 8^3 block of owned nodes
@@ -593,13 +619,14 @@ __device__ __forceinline__ void weight_fx_adjoint(const float w[3][3], const flo
 // g2p_opt.grad: adjoints of level s+1 -> x[s], F[s], and the v_out.grad
 // contributions scattered through the chunk's fixed-point window to its slot.
 __global__ __launch_bounds__(kChunk) void k_g2p_bwd(View V, int s, float dt) {
-  __shared__ unsigned long long win[3 * kWin3];
+  __shared__ __align__(16) unsigned long long win[3 * kWin3];
+  __shared__ __align__(16) int wlo[3 * kWin3];
   __shared__ float s_max[4];
   const float* const vout = glv(V.vout, V, s);
   const int c = blockIdx.x;
   if (c >= V.nchunks[s]) return;
   const int4 rec = V.chunks[(size_t)s * V.max_chunks + c];
-  for (int l = threadIdx.x; l < 3 * kWin3; l += kChunk) win[l] = 0ull;
+  zero_window<3>(win, wlo);
   const int tz = rec.x % V.nta, ty = (rec.x / V.nta) % V.nta, tx = rec.x / (V.nta * V.nta);
   const int ox = tx * kTile, oy = ty * kTile, oz = tz * kTile;
   const bool on = (int)threadIdx.x < rec.z;
@@ -667,7 +694,7 @@ __global__ __launch_bounds__(kChunk) void k_g2p_bwd(View V, int s, float dt) {
   int S[3];
   S[0] = S[1] = S[2] = chunk_exponent(bound, s_max, 0);  // its barrier also orders the zeroing
   if (on) {
-    const double sc = ldexp(1.0, S[0]);
+    const Scale sc = make_scale(S[0]);
     const int lb0 = base[0] - ox, lb1 = base[1] - oy, lb2 = base[2] - oz;
     float gfx[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -700,7 +727,7 @@ __global__ __launch_bounds__(kChunk) void k_g2p_bwd(View V, int s, float dt) {
               g_dpos[cc] += gC1[r * 3 + cc] * gv[r] * cw;
               g_gw[cc] += g_nF[r * 3 + cc] * gv[r];
             }
-            if (in_win) lds_add(&win[r * kWin3 + l], to_fixed(g_g, sc));
+            if (in_win) lds_add(win, wlo, r * kWin3 + l, g_g, sc);
           }
           weight_fx_adjoint(w, dw, i, j, k, V.inv_dx, g_weight, g_gw, gfx);
           for (int d = 0; d < 3; ++d) gfx[d] -= g_dpos[d];
@@ -708,7 +735,7 @@ __global__ __launch_bounds__(kChunk) void k_g2p_bwd(View V, int s, float dt) {
     for (int d = 0; d < 3; ++d) pl(V.gx, V, s, 3, d)[p] += gfx[d] * V.inv_dx;
   }
   __syncthreads();
-  store_window(V, win, 3, S, c);
+  store_window(V, win, wlo, 3, S, c);
 }
 
 // grid_normalization_and_gravity.grad: v_out.grad += this substep's window

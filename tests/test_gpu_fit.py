@@ -17,6 +17,10 @@ Tolerances (max-abs error over the reference's max-abs value):
   measured GPU-vs-GPU run-to-run spreads of up to 2.07e-2 there (12 runs),
   equal to the GPU-vs-oracle maximum, with medians of 2e-6.
   learn: logE/y 1e-5 absolute after one step.
+These tolerances guard the 30-substep chain.  The accuracy of a single
+substep's adjoints (every particle, model and grid adjoint, per element) is
+pinned by test_gpu_fit_ref.py against the float64 autograd reference of
+fit_ref.py, at 4 x the oracle's own distance from it.
 """
 from __future__ import annotations
 
