@@ -757,7 +757,9 @@ __device__ __forceinline__ void grid_work(int b, int it, int S, int& P, int& par
     P = (k * 8 + x) * kGridGroup + (u - k * kGridGroup);
   }
 }
-template <bool SLAB>
+// EXT: node_update's, for a table that holds extended collider records
+// (launch_grid_f; never with SLAB, whose handles refuse such records)
+template <bool SLAB, bool EXT = false>
 __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_grid_f(GridDims g, FTiles tl, ChunkIn ck, const int* __restrict__ tbox,
                                                     const float4* __restrict__ slots, float4* __restrict__ gacc,
                                                     float4* __restrict__ gvel, const BcTable* __restrict__ bct,
@@ -881,11 +883,11 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
       if (inrect) {
       } else if (!kGridSkip0 || a.w != 0.f || (reach && GSMPM_GRID_SKIP0 == 1)) {
         if constexpr (kGvelStore == 1)
-          nt_store4(gvel + idx, node_update(a, i, j, k, g, gs, bct));
+          nt_store4(gvel + idx, node_update<EXT>(a, i, j, k, g, gs, bct));
         else if constexpr (kGvelStore == 2)
-          wt_store4(gvel + idx, node_update(a, i, j, k, g, gs, bct));
+          wt_store4(gvel + idx, node_update<EXT>(a, i, j, k, g, gs, bct));
         else
-          gvel[idx] = node_update(a, i, j, k, g, gs, bct);
+          gvel[idx] = node_update<EXT>(a, i, j, k, g, gs, bct);
       }
     }
     if (it == 0) stamp(3, 4);

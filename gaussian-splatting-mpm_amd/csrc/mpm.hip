@@ -491,9 +491,83 @@ struct GridStep {
   int keep;
 };
 
+// Extended collider records (kind 2: plane, ball, box or walls with a sticky
+// / slip / separate surface, a damping factor and an activity bit; gsmpm.h
+// gsmpm_mpm_add_collider, DESIGN.md "Extended colliders").  All f32, unfused,
+// left to right.  A record's shape and surface are uniform, so the branches
+// on them are scalar.
+// The response to one normal n (unit, out of the collider), without the
+// damping: sticky zeroes v; separate removes the inward normal component,
+// slip the whole of it; then Coulomb friction on what is left, as
+// collider.py:30-41.
+__device__ __forceinline__ void collide_ext(float (&v)[3], const float (&n)[3], int surface, float mu) {
+  if (surface == kSurfSticky) {
+    v[0] = 0.f;
+    v[1] = 0.f;
+    v[2] = 0.f;
+    return;
+  }
+  const float nc = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
+  const float mn = surface == kSurfSeparate ? fminf(nc, 0.0f) : nc;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) v[d] = v[d] - mn * n[d];
+  const float len = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  if (nc < 0.0f && len > 1e-20f) {
+    const float sc = fmaxf(0.0f, len + nc * mu);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[d] = sc * (v[d] / len);
+  }
+}
+
+// one extended record on the node at p
+__device__ __forceinline__ void apply_ext(float (&v)[3], const float (&p)[3], const GridOp& op, const GridOpExt& ex) {
+  const float d[3] = {p[0] - op.a[0], p[1] - op.a[1], p[2] - op.a[2]};
+  const int surface = ex.surface;
+  bool hit = false;
+  if (ex.shape == kShapeWalls) {
+    // everything outside the box: one response per violated axis, in axis order
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+      if (fabsf(d[ax]) > op.b[ax]) {
+        float n[3] = {0.f, 0.f, 0.f};
+        n[ax] = d[ax] < 0.0f ? 1.0f : -1.0f;
+        collide_ext(v, n, surface, op.friction);
+        hit = true;
+      }
+    }
+  } else {
+    float n[3] = {op.b[0], op.b[1], op.b[2]};
+    int surf = surface;
+    if (ex.shape == kShapePlane) {
+      hit = d[0] * n[0] + d[1] * n[1] + d[2] * n[2] < 0.0f;
+    } else if (ex.shape == kShapeBall) {
+      const float L = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      hit = L < op.b[0];
+      if (L <= 1e-20f) surf = kSurfSticky;  // no normal at the centre
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) n[ax] = d[ax] / L;
+    } else {  // box: the face of least penetration, the first axis on a tie
+      const float q0 = op.b[0] - fabsf(d[0]), q1 = op.b[1] - fabsf(d[1]), q2 = op.b[2] - fabsf(d[2]);
+      hit = fabsf(d[0]) < op.b[0] && fabsf(d[1]) < op.b[1] && fabsf(d[2]) < op.b[2];
+      const int ax = (q0 <= q1 && q0 <= q2) ? 0 : (q1 <= q2 ? 1 : 2);
+#pragma unroll
+      for (int e = 0; e < 3; ++e) n[e] = e == ax ? (d[e] < 0.0f ? -1.0f : 1.0f) : 0.0f;
+    }
+    if (hit) collide_ext(v, n, surf, op.friction);
+  }
+  if (hit && surface != kSurfSticky) {
+#pragma unroll
+    for (int e = 0; e < 3; ++e) v[e] = v[e] * ex.damping;
+  }
+}
+
 // grid_normalization_and_gravity (utils.py:177-183) and the grid_postprocess
 // list (solver.py:41-46) of one node: BasicBC.apply (boundary_conditions.py:
 // 23-27) / MPM_Collider.collide (collider.py:13-44), pointwise, in list order.
+// EXT: the table may hold extended records too.  The plain instantiation is
+// the code it always was; the host launches an EXT kernel only for a table
+// that holds such a record (grid_ext).
+template <bool EXT = false>
 __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int k, const GridDims& g,
                                               const GridStep& gs, const BcTable* __restrict__ bct) {
   float v[3] = {0.f, 0.f, 0.f};
@@ -512,6 +586,10 @@ __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int
           v[1] = 0.f;
           v[2] = 0.f;
         }
+      } else if (EXT && op.kind == 2) {
+        if (!((gs.mask >> op.bit) & 1u)) continue;
+        const float p[3] = {p0, p1, p2};
+        apply_ext(v, p, op, bct->ext[o]);
       } else {
         const float o0 = p0 - op.a[0], o1 = p1 - op.a[1], o2 = p2 - op.a[2];
         const float dot = o0 * op.b[0] + o1 * op.b[1] + o2 * op.b[2];
@@ -593,6 +671,8 @@ __device__ __forceinline__ float4 node_sum(const float4* __restrict__ slots, int
   return a;
 }
 
+// EXT: node_update's (launch_grid picks it for a table with extended records)
+template <bool EXT>
 __global__ __launch_bounds__(512) void k_grid(GridDims g, Tiles tl, ChunkIn ck, const float4* __restrict__ slots,
                                               float4* __restrict__ gacc, float4* __restrict__ gvel,
                                               const BcTable* __restrict__ bct, GridStep gs,
@@ -631,7 +711,7 @@ __global__ __launch_bounds__(512) void k_grid(GridDims g, Tiles tl, ChunkIn ck, 
         a.w += o.w;
         gacc[idx] = gs.keep ? a : make_float4(0.f, 0.f, 0.f, 0.f);
       }
-      gvel[idx] = node_update(a, i, j, k, g, gs, bct);
+      gvel[idx] = node_update<EXT>(a, i, j, k, g, gs, bct);
     }
   }
 }
@@ -1639,6 +1719,7 @@ struct gsmpm_mpm {
   BcTable host_bc{};
   BcTable* dev_bc = nullptr;
   int n_bc = 0;
+  int n_ext = 0;  // extended collider records in host_bc: > 0 selects the EXT grid kernels (grid_ext)
   bool has_particles = false;
   bool has_R = false;  // a gsmpm_mpm_postprocess ran since the particles were set (gsmpm_mpm_sh_rotations)
   hipStream_t cap = nullptr;
@@ -2175,12 +2256,24 @@ static int substep_begin(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream
   return GSMPM_OK;
 }
 
+// Extended collider records select the EXT instantiation of the grid kernels
+// (k_grid, k_grid_f); a table of fixed cubes and legacy planes runs the plain
+// ones, as k_fused_mixed / k_preprocess<true> are picked only for their scenes.
+static bool grid_ext(const gsmpm_mpm* h) { return h->n_ext > 0; }
+
+static void launch_grid(gsmpm_mpm* h, int c, const GridStep& gs, hipStream_t st, const hipEvent_t* ev) {
+  if (grid_ext(h))
+    launch(ev, k_grid<true>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
+           (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, gs, bin_out(h, c ^ 1));
+  else
+    launch(ev, k_grid<false>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
+           (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, gs, bin_out(h, c ^ 1));
+}
+
 // Second half: grid update, G2P, binning of parity nx.
 static int substep_end(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream_t st, const hipEvent_t* e8) {
   const int nx = c ^ 1;
-  launch(e8 ? e8 + 2 : nullptr, k_grid, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
-         (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask),
-         bin_out(h, nx));
+  launch_grid(h, c, grid_step(h, dt, mask), st, e8 ? e8 + 2 : nullptr);
   GSMPM_LAUNCH_CHECK();
   launch(e8 ? e8 + 4 : nullptr, k_g2p, dim3(g2p_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl,
          chunk_in(h, c), bin_out(h, nx), (const float4*)h->gvel, dt);
@@ -2370,6 +2463,9 @@ static int launch_grid_f(gsmpm_mpm* h, int wp, float dt, uint32_t mask, const Gr
   if (swp)
     launch(ev, k_grid_f<true>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots, gb.gacc,
            h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
+  else if (grid_ext(h))
+    launch(ev, k_grid_f<false, true>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots,
+           gb.gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
   else
     launch(ev, k_grid_f<false>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots, gb.gacc,
            h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
@@ -3038,6 +3134,56 @@ int gsmpm_mpm_add_plane_collider(gsmpm_mpm* h, const double p[3], const double n
   return rc ? rc : id;
 }
 
+// An extended collider record (no reference counterpart beyond the unused
+// arguments of solver.py:140-147).  Refused, with nothing changed, where no
+// EXT grid update exists: a slab's grid pass (slab.h) and the folded staging
+// of k_fused (GSMPM_FOLD=1) apply the plain node_update.
+int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* c) {
+  GSMPM_REQUIRE(h && c, "gsmpm_mpm_add_collider: null argument");
+  if (h->slab) {
+    set_error("gsmpm_mpm_add_collider: extended colliders are not supported on a slab of a multi-GPU domain "
+              "(its grid passes apply fixed cubes and plane colliders only)");
+    return GSMPM_ESTATE;
+  }
+  if (h->fold) {
+    set_error("gsmpm_mpm_add_collider: extended colliders are not supported by the folded pipeline (GSMPM_FOLD=1)");
+    return GSMPM_ESTATE;
+  }
+  GSMPM_REQUIRE(c->shape >= GSMPM_SHAPE_PLANE && c->shape <= GSMPM_SHAPE_WALLS, "gsmpm_mpm_add_collider: unknown shape");
+  GSMPM_REQUIRE(c->surface >= GSMPM_SURF_STICKY && c->surface <= GSMPM_SURF_SEPARATE,
+                "gsmpm_mpm_add_collider: unknown surface");
+  GSMPM_REQUIRE(c->friction >= 0, "gsmpm_mpm_add_collider: negative friction");  // false for NaN too
+  GSMPM_REQUIRE(c->surface != GSMPM_SURF_STICKY || c->friction == 0,
+                "gsmpm_mpm_add_collider: a sticky surface takes friction 0");
+  double b[3] = {c->b[0], c->b[1], c->b[2]};
+  if (c->shape == GSMPM_SHAPE_PLANE) {
+    const double nn = b[0] * b[0] + b[1] * b[1] + b[2] * b[2];
+    GSMPM_REQUIRE(nn > 0, "gsmpm_mpm_add_collider: zero normal");
+    const double sc = 1.0 / std::sqrt(nn);  // f64, as gsmpm_mpm_add_plane_collider
+    for (int d = 0; d < 3; ++d) b[d] = sc * b[d];
+  } else if (c->shape == GSMPM_SHAPE_BALL) {
+    GSMPM_REQUIRE(b[0] > 0, "gsmpm_mpm_add_collider: radius must be positive");
+    b[1] = b[2] = 0.0;
+  } else {
+    GSMPM_REQUIRE(b[0] > 0 && b[1] > 0 && b[2] > 0, "gsmpm_mpm_add_collider: half extents must be positive");
+  }
+  const int id = add_bc_common(h);
+  if (id < 0) return GSMPM_EINVAL;
+  const int o = h->host_bc.n_ops++;
+  GridOp& op = h->host_bc.op[o];
+  op.kind = 2;
+  op.bit = id;
+  for (int d = 0; d < 3; ++d) {
+    op.a[d] = (float)c->a[d];
+    op.b[d] = (float)b[d];
+  }
+  op.friction = (float)c->friction;
+  h->host_bc.ext[o] = GridOpExt{c->shape, c->surface, (float)c->damping};
+  ++h->n_ext;
+  int rc = upload_bc(h);
+  return rc ? rc : id;
+}
+
 namespace gsmpm {
 // The re-binnings of the next step call (fused pipeline, one domain): enough
 // that no particle moves more than 0.8 cell between two of them, from the
@@ -3423,10 +3569,7 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
   hipEvent_t e[2];
   GSMPM_HIP(hipEventCreate(&e[0]));
   GSMPM_HIP(hipEventCreate(&e[1]));
-  auto grid = [&]() {
-    launch(nullptr, k_grid, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c), (const float4*)h->ph.slots,
-           h->gacc, h->gvel, (const BcTable*)h->dev_bc, gs, bin_out(h, nx));
-  };
+  auto grid = [&]() { launch_grid(h, c, gs, st, nullptr); };
   auto g2p = [&]() {
     launch(nullptr, k_g2p, dim3(g2p_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
            bin_out(h, nx), (const float4*)h->gvel, dt);

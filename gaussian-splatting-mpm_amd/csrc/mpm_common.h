@@ -49,14 +49,26 @@ struct Impulse {
   int bit;
 };
 struct GridOp {
-  int kind;  // 0 fixed cube, 1 plane collider
+  int kind;  // 0 fixed cube, 1 plane collider, 2 extended collider (its shape, surface and damping in BcTable::ext)
   int bit;
   float a[3], b[3], friction;
+};
+// Extended collider records (gsmpm_mpm_add_collider): GridOp o of kind 2
+// holds the geometry -- a = point / centre, b = unit normal (plane), radius
+// in b[0] (ball), half extents (box, walls) -- and the friction; ext[o] the
+// rest.  Only the EXT instantiations of the grid kernels read them, and a
+// table without such a record is updated by the plain ones.
+enum ColliderShape : int { kShapePlane = 0, kShapeBall = 1, kShapeBox = 2, kShapeWalls = 3 };
+enum ColliderSurface : int { kSurfSticky = 0, kSurfSlip = 1, kSurfSeparate = 2 };
+struct GridOpExt {
+  int shape, surface;
+  float damping;
 };
 struct BcTable {
   int n_imp, n_ops;
   Impulse imp[kMaxBC];
   GridOp op[kMaxBC];
+  GridOpExt ext[kMaxBC];  // parallel to op[], after it: the offsets the plain instantiations read do not move
 };
 
 #ifndef GSMPM_PSTORE

@@ -614,6 +614,11 @@ int gsmpm_mpm_slab_init(gsmpm_mpm* h, int32_t rank, int32_t world, int32_t lo, i
               "(the migration payload does not carry the ids)");
     return GSMPM_ESTATE;
   }
+  if (h->n_ext > 0) {
+    set_error("gsmpm_mpm_slab_init: the handle holds extended colliders (gsmpm_mpm_add_collider), which slabs do "
+              "not support (their grid passes apply fixed cubes and plane colliders only)");
+    return GSMPM_ESTATE;
+  }
   GSMPM_REQUIRE(h->fused, "gsmpm_mpm_slab_init: slabs run the fused pipeline (no GSMPM_FLAG_PHASED / KEEP_GRID)");
   GSMPM_REQUIRE(!h->has_particles, "gsmpm_mpm_slab_init: call before setting particles");
   GSMPM_REQUIRE(!h->slab, "gsmpm_mpm_slab_init: already a slab");

@@ -39,6 +39,15 @@ class MpmParams(ctypes.Structure):
     ]
 
 
+class Collider(ctypes.Structure):
+    """gsmpm_collider (include/gsmpm.h)."""
+    _fields_ = [
+        ("shape", ctypes.c_int32), ("surface", ctypes.c_int32),
+        ("a", ctypes.c_double * 3), ("b", ctypes.c_double * 3),
+        ("friction", ctypes.c_double), ("damping", ctypes.c_double),
+    ]
+
+
 class RasterArgs(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32), ("D", ctypes.c_int32), ("M", ctypes.c_int32),
@@ -78,6 +87,7 @@ _SIGS = {
                                              ctypes.c_double * 3, ctypes.c_double]),
     "gsmpm_mpm_add_plane_collider": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
                                                     ctypes.c_double]),
+    "gsmpm_mpm_add_collider": (ctypes.c_int, [c_void_p, ctypes.POINTER(Collider)]),
     "gsmpm_mpm_step": (ctypes.c_int, [c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32),
                                       c_void_p]),
     "gsmpm_rccl_unique_id": (ctypes.c_int, [c_void_p]),
@@ -197,6 +207,9 @@ FIT_FIELD = {k: i for i, k in enumerate(
      "glam", "cov", "gcov", "init_cov", "vol", "mass"))}
 FLAG_JELLY_FCR, FLAG_KEEP_GRID, FLAG_NO_GRAPH, FLAG_NO_SORT, FLAG_PHASED = 1, 2, 4, 8, 16
 PIPE_PHASED, PIPE_FUSED = 0, 1
+# extended colliders (gsmpm_mpm_add_collider)
+SHAPE = {"plane": 0, "ball": 1, "box": 2, "walls": 3}
+SURFACE = {"sticky": 0, "slip": 1, "separate": 2}
 
 
 class GsmpmError(RuntimeError):

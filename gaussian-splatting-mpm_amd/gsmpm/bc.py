@@ -5,6 +5,9 @@ The reference decides BC activity on the host from a float64 clock:
 and ``BasicBC.isActive`` = ``start_time <= time < start_time + substep_dt*num_dt``
 (mpm_solver/boundary_conditions.py:15-16,30-31), evaluated before the substep's
 kernels run.  Colliders bypass the test (``isCollide``, solver.py:42-43).
+Extended colliders (gsmpm_mpm_add_collider, not in the reference) do not:
+their spec kind, ``"windowed_collider"``, is active on the substeps where
+``start_time <= time < end_time`` on the same clock.
 
 This module reproduces that clock exactly (same float64 additions in the same
 order) and turns it into one activity bit-mask per substep for
@@ -18,7 +21,7 @@ from dataclasses import dataclass, field
 
 @dataclass
 class BCSpec:
-    kind: str              # "fixed_cube" | "impulse" | "collider"
+    kind: str              # "fixed_cube" | "impulse" | "collider" (always on) | "windowed_collider"
     bit: int               # id returned by the library (bit of the activity mask)
     start_time: float = 0.0
     end_time: float = float("inf")
@@ -28,6 +31,12 @@ class BCSpec:
         if self.kind == "collider":
             return True
         return self.start_time <= time < self.end_time
+
+
+def windowed_collider(bit, start_time=0.0, end_time=999.0, **params):
+    """The spec of an extended collider: active while start_time <= time <
+    end_time (defaults: add_surface_collider's, solver.py:140-147)."""
+    return BCSpec("windowed_collider", int(bit), float(start_time), float(end_time), dict(params))
 
 
 def bc_window(start_time, substep_dt, num_dt):

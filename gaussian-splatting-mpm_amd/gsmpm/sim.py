@@ -86,6 +86,31 @@ class Simulator:
         return check(LIB.gsmpm_mpm_add_plane_collider(self._h, _d3(point), _d3(normal), float(friction)),
                      "add_plane_collider")
 
+    def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, *, point=None, normal=None,
+                     center=None, radius=None, half=None) -> int:
+        """An extended collider (gsmpm_mpm_add_collider; no reference counterpart):
+        ``shape`` "plane" (point, normal), "ball" (center, radius), "box" or
+        "walls" (center, half: a solid box / everything outside it), ``surface``
+        "sticky", "slip" or "separate".  Returns its bit of the activity mask,
+        which -- unlike the legacy plane collider's -- it honours."""
+        if shape not in _lib.SHAPE:
+            raise ValueError(f"add_collider: unknown shape {shape!r} (one of {sorted(_lib.SHAPE)})")
+        if surface not in _lib.SURFACE:
+            raise ValueError(f"add_collider: unknown surface {surface!r} (one of {sorted(_lib.SURFACE)})")
+        want = {"plane": ("point", "normal"), "ball": ("center", "radius")}.get(shape, ("center", "half"))
+        given = {"point": point, "normal": normal, "center": center, "radius": radius, "half": half}
+        extra = [k for k, v in given.items() if v is not None and k not in want]
+        missing = [k for k in want if given[k] is None]
+        if extra or missing:
+            raise TypeError(f"add_collider: a {shape} takes {want[0]} and {want[1]}"
+                            + (f"; missing {missing}" if missing else "") + (f"; unexpected {extra}" if extra else ""))
+        c = _lib.Collider()
+        c.shape, c.surface = _lib.SHAPE[shape], _lib.SURFACE[surface]
+        c.a[:] = [float(a) for a in given[want[0]]]
+        c.b[:] = [float(radius), 0.0, 0.0] if shape == "ball" else [float(a) for a in given[want[1]]]
+        c.friction, c.damping = float(friction), float(damping)
+        return check(LIB.gsmpm_mpm_add_collider(self._h, ctypes.byref(c)), "add_collider")
+
     # ------------------------------------------------ per-particle materials --
     @property
     def material_mode(self) -> int:

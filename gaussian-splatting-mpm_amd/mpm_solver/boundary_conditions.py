@@ -131,11 +131,45 @@ class StickyGroundBC(BasicBC):
         return True
 
 
+class ColliderBC:
+    """collider (not in the reference, whose add_surface_collider declares
+    surface / start_time / end_time and never uses them, solver.py:140-147): an
+    extended collider record -- shape "plane" (point, normal), "ball" (center,
+    radius), "box" or "walls" (center, half), surface "sticky" / "slip" /
+    "separate", friction, damping -- active while start_time <= time <
+    end_time on the host's float64 clock.  The per-node work runs in the EXT
+    grid kernels (gsmpm_mpm_add_collider).  isCollide stays False: unlike the
+    legacy plane collider this one honours its window."""
+
+    _geometry = {"plane": ("point", "normal"), "ball": ("center", "radius"), "box": ("center", "half"),
+                 "walls": ("center", "half")}
+
+    def __init__(self, n_particles, bc_args, sim_args=None):
+        self.n_particles = n_particles
+        self.id = bc_args.get("id")
+        self.type = "collider"
+        self.shape = bc_args["shape"]
+        if self.shape not in self._geometry:
+            raise ValueError(f"collider: unknown shape {self.shape!r} (one of {sorted(self._geometry)})")
+        self.surface = bc_args.get("surface", "separate")
+        self.friction = float(bc_args.get("friction", 0.0))
+        self.damping = float(bc_args.get("damping", 1.0))
+        self.start_time = float(bc_args.get("start_time", 0.0))
+        self.end_time = float(bc_args.get("end_time", 999.0))
+        self.geometry = {k: bc_args[k] for k in self._geometry[self.shape]}  # KeyError names the missing one
+        self.isCollide = False
+        self.bit = None  # library bc id (bit of the activity mask)
+
+    def isActive(self, time):
+        return time >= self.start_time and time < self.end_time
+
+
 # boundary_conditions.py:97-109 -- note preprocess_bc is a *string*, so
 # ``type in preprocess_bc`` is a substring test exactly as in the reference.
 preprocess_bc = ("impulse")
 postprocess_bc = ("fixed_cube", "sticky_ground")
 init_bc = ("additional_params", "modify_material")
+collider_bc = ("collider",)  # extended colliders: grid_postprocess entries with a window of their own
 
 boundaryConditionTypeCallBacks = {
     "fixed_cube": BasicBC,
@@ -143,4 +177,5 @@ boundaryConditionTypeCallBacks = {
     "sticky_ground": StickyGroundBC,
     "additional_params": MaterialParamsModifier,
     "modify_material": MaterialTypeModifier,
+    "collider": ColliderBC,
 }

@@ -18,8 +18,8 @@ import math
 
 from gsmpm.fit import FitSimulator
 from gsmpm.sim import Simulator
-from mpm_solver.boundary_conditions import (StickyGroundBC, boundaryConditionTypeCallBacks, init_bc,
-                                            postprocess_bc, preprocess_bc)
+from mpm_solver.boundary_conditions import (ColliderBC, StickyGroundBC, boundaryConditionTypeCallBacks, collider_bc,
+                                            init_bc, postprocess_bc, preprocess_bc)
 from mpm_solver.collider import MPM_Collider, collideTypeCallBacks
 from mpm_solver.model import MPM_model, MPM_state, MPM_state_opt
 
@@ -114,6 +114,9 @@ class MPM_Simulator:
     def set_boundary_conditions(self, bc_args_arr, sim_args):
         if self.fitting:
             for bc_args in bc_args_arr:
+                if bc_args["type"] in collider_bc:
+                    raise TypeError("collider records apply to the forward-only simulator; the fitting path "
+                                    "(MPM_state_opt) has no extended colliders")
                 bc = boundaryConditionTypeCallBacks[bc_args["type"]](self.n_particles, bc_args, sim_args)
                 if bc.type in postprocess_bc:
                     self.grid_postprocess.append(bc)
@@ -129,6 +132,8 @@ class MPM_Simulator:
             if bc.type in postprocess_bc:
                 bc.bit = self._sim.add_fixed_cube(bc.center, bc.size)
                 self.grid_postprocess.append(bc)
+            if bc.type in collider_bc:
+                self._add_collider_bc(bc)
             if bc.type in init_bc:
                 self.init_particles.append(bc)
         # solver.py:125-129, in list order (a later box overrides an earlier one).  An
@@ -157,6 +162,29 @@ class MPM_Simulator:
             return
         cl.bit = self._sim.add_plane_collider(point, normal, friction)
         self.grid_postprocess.append(cl)
+
+    def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, start_time=0.0, end_time=999.0,
+                     **geometry):
+        """An extended collider (not in the reference; add_surface_collider above
+        stays the legacy plane): ``shape`` "plane" (point=, normal=), "ball"
+        (center=, radius=), "box" or "walls" (center=, half=); ``surface``
+        "sticky", "slip" or "separate"; active on the substeps where
+        start_time <= time < end_time.  Returns the descriptor (its ``bit`` is
+        the library's bc id).  Same record as a ``{"type": "collider", ...}``
+        entry of set_boundary_conditions."""
+        if self.fitting:
+            raise TypeError("add_collider applies to the forward-only simulator; the fitting path (MPM_state_opt) "
+                            "has no extended colliders")
+        bc = ColliderBC(self.n_particles, dict(geometry, type="collider", shape=shape, surface=surface,
+                                               friction=friction, damping=damping, start_time=start_time,
+                                               end_time=end_time))
+        self._add_collider_bc(bc)
+        return bc
+
+    def _add_collider_bc(self, bc):
+        self.flush()  # substeps queued so far ran without it
+        bc.bit = self._sim.add_collider(bc.shape, bc.surface, bc.friction, bc.damping, **bc.geometry)
+        self.grid_postprocess.append(bc)
 
     # ------------------------------------------- differentiable (fitting) --
     def _need_fit(self, name):

@@ -86,6 +86,51 @@ int gsmpm_mpm_add_impulse(gsmpm_mpm* h, const double center[3], const double siz
                           double substep_dt);
 int gsmpm_mpm_add_plane_collider(gsmpm_mpm* h, const double point[3], const double normal[3], double friction);
 
+/* Extended colliders: a shape, a surface, friction, damping and an activity
+ * bit.  No reference counterpart beyond the arguments that
+ * add_surface_collider declares and never uses (surface, start_time,
+ * end_time: "For now, not used", solver.py:140-147); the semantics are this
+ * library's (DESIGN.md "Extended colliders").  Unlike the legacy plane a
+ * record honours its bit of bc_active (NULL: active), so the caller can
+ * switch it on and off in time.  Only nodes with mass > 1e-15 are touched;
+ * records apply in table order, mixed freely with fixed cubes and legacy
+ * planes; all arithmetic is f32, unfused, left to right, on the node
+ * p = (i dx, j dx, k dx).  Geometry is converted to f32 here.
+ *   shape     a        b                  inside the collider    normal n (out of it)
+ *   PLANE     point    normal (f64-       (p - a) . n < 0        n
+ *                      normalised here)
+ *   BALL      centre   radius in b[0]     |p - a| < radius       (p - a) / |p - a|   (sticky where |p - a| <= 1e-20)
+ *   BOX       centre   half extents       |d_x| < b_x, all x     sign(d_x*) e_x*, x* the first axis of least b_x - |d_x|
+ *   WALLS     centre   half extents       |d_x| > b_x, any x     -sign(d_x) e_x for each violated axis in turn
+ * Response with nc = v . n:
+ *   STICKY    v = 0 (friction must be 0; damping ignored)
+ *   SEPARATE  v -= min(nc, 0) n      SLIP  v -= nc n
+ *   then, for both, if nc < 0 and |v| > 1e-20: v = max(0, |v| + nc friction) v / |v|; then v *= damping
+ *   (WALLS: damping once, after the axis loop, if any axis fired).
+ * PLANE + SEPARATE + damping 0.99f is, operation for operation,
+ * gsmpm_mpm_add_plane_collider's update.
+ * Returns the bc id (shared with the other BCs, at most 32), or GSMPM_EINVAL:
+ * unknown shape or surface, radius or a half extent <= 0, zero normal,
+ * negative friction, STICKY with friction != 0, too many BCs.  GSMPM_ESTATE,
+ * with a message and nothing changed: a slab handle (and gsmpm_mpm_slab_init
+ * refuses a handle that holds such records), or a handle created with
+ * GSMPM_FOLD=1.  A handle without extended records launches the grid kernels
+ * it always did; the first record switches it to their EXT instantiations. */
+#define GSMPM_SHAPE_PLANE 0
+#define GSMPM_SHAPE_BALL 1
+#define GSMPM_SHAPE_BOX 2
+#define GSMPM_SHAPE_WALLS 3
+#define GSMPM_SURF_STICKY 0
+#define GSMPM_SURF_SLIP 1
+#define GSMPM_SURF_SEPARATE 2
+typedef struct {
+  int32_t shape, surface;  /* GSMPM_SHAPE_*, GSMPM_SURF_* */
+  double a[3], b[3];       /* geometry, by shape (table above) */
+  double friction;         /* Coulomb coefficient, >= 0 */
+  double damping;          /* factor on v of a node the collider acted on (1: none); stored as f32 */
+} gsmpm_collider;
+int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* collider);
+
 /* MPM_Simulator.p2g2p (solver.py:27-52) x n_substeps.  bc_active[s] holds
  * the activity bits of substep s, decided by the caller from the f64 host
  * clock exactly as BasicBC.isActive (boundary_conditions.py:30-31); NULL =
