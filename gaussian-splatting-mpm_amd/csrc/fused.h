@@ -758,12 +758,13 @@ __device__ __forceinline__ void grid_work(int b, int it, int S, int& P, int& par
   }
 }
 // EXT: node_update's, for a table that holds extended collider records
-// (launch_grid_f; never with SLAB, whose handles refuse such records)
-template <bool SLAB, bool EXT = false>
+// (launch_grid_f; never with SLAB, whose handles refuse such records);
+// GS = GridStepT: its MOV form, for a table that holds moving records
+template <bool SLAB, bool EXT = false, class GS = GridStep>
 __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_grid_f(GridDims g, FTiles tl, ChunkIn ck, const int* __restrict__ tbox,
                                                     const float4* __restrict__ slots, float4* __restrict__ gacc,
                                                     float4* __restrict__ gvel, const BcTable* __restrict__ bct,
-                                                    GridStep gs, const int* __restrict__ esc_in,
+                                                    GS gs, const int* __restrict__ esc_in,
                                                     int* __restrict__ esc_clear, int* __restrict__ zc,
                                                     int* __restrict__ zf, SlabWin sw) {
   sim_prio();

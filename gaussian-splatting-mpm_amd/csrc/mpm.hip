@@ -33,6 +33,7 @@
 #include <cstring>
 #include <map>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -490,6 +491,15 @@ struct GridStep {
   uint32_t mask;
   int keep;
 };
+// The step argument of the MOV instantiations (tables with a moving record,
+// gsmpm_mpm_step_timed): GridStep plus where the substep's time is -- entry s
+// of the handle's device table of caller times, written in stream order
+// before the call's substeps.  s is baked into the launch (and so into a
+// captured graph), the time is not.
+struct GridStepT : GridStep {
+  const float* times;
+  int s;
+};
 
 // Extended collider records (kind 2: plane, ball, box or walls with a sticky
 // / slip / separate surface, a damping factor and an activity bit; gsmpm.h
@@ -519,9 +529,10 @@ __device__ __forceinline__ void collide_ext(float (&v)[3], const float (&n)[3], 
   }
 }
 
-// one extended record on the node at p
-__device__ __forceinline__ void apply_ext(float (&v)[3], const float (&p)[3], const GridOp& op, const GridOpExt& ex) {
-  const float d[3] = {p[0] - op.a[0], p[1] - op.a[1], p[2] - op.a[2]};
+// one extended record, placed at c, on the node at p; true where it hit the node
+__device__ __forceinline__ bool apply_ext_at(float (&v)[3], const float (&p)[3], const float (&c)[3], const GridOp& op,
+                                             const GridOpExt& ex) {
+  const float d[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
   const int surface = ex.surface;
   bool hit = false;
   if (ex.shape == kShapeWalls) {
@@ -559,6 +570,32 @@ __device__ __forceinline__ void apply_ext(float (&v)[3], const float (&p)[3], co
 #pragma unroll
     for (int e = 0; e < 3; ++e) v[e] = v[e] * ex.damping;
   }
+  return hit;
+}
+__device__ __forceinline__ void apply_ext(float (&v)[3], const float (&p)[3], const GridOp& op, const GridOpExt& ex) {
+  (void)apply_ext_at(v, p, op.a, op, ex);
+}
+
+// One moving record at caller time t (DESIGN.md "Moving colliders"): the
+// record stands at a before t0, translates with w inside [t0, t1) and stands
+// where it arrived from t1 on; the response acts on the velocity relative to
+// the collider's, and only a node the record hits is rewritten.
+__device__ __forceinline__ void apply_mov(float (&v)[3], const float (&p)[3], const GridOp& op, const GridOpExt& ex,
+                                          const GridOpMov& mv, float t) {
+  const float tc = fminf(fmaxf(t, mv.t0), mv.t1);
+  const float tau = tc - mv.t0;
+  const bool mov = t >= mv.t0 && t < mv.t1;
+  float c[3], wc[3], u[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    c[d] = op.a[d] + mv.w[d] * tau;
+    wc[d] = mov ? mv.w[d] : 0.0f;
+    u[d] = v[d] - wc[d];
+  }
+  if (apply_ext_at(u, p, c, op, ex)) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[d] = u[d] + wc[d];
+  }
 }
 
 // grid_normalization_and_gravity (utils.py:177-183) and the grid_postprocess
@@ -567,15 +604,26 @@ __device__ __forceinline__ void apply_ext(float (&v)[3], const float (&p)[3], co
 // EXT: the table may hold extended records too.  The plain instantiation is
 // the code it always was; the host launches an EXT kernel only for a table
 // that holds such a record (grid_ext).
-template <bool EXT = false>
+// GS = GridStepT (MOV, with EXT): the table may hold moving records too
+// (grid_mov); the substep's time is one uniform word of the caller's table,
+// read through the constant address space so that it is a scalar load issued
+// with the table's.
+template <bool EXT = false, class GS = GridStep>
 __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int k, const GridDims& g,
-                                              const GridStep& gs, const BcTable* __restrict__ bct) {
+                                              const GS& gs, const BcTable* __restrict__ bct) {
+  constexpr bool MOV = std::is_same<GS, GridStepT>::value;
+  static_assert(!MOV || EXT, "moving records are extended records");
   float v[3] = {0.f, 0.f, 0.f};
   if (a.w > 1e-15f) {
     v[0] = a.x / a.w + gs.dgx;
     v[1] = a.y / a.w + gs.dgy;
     v[2] = a.z / a.w + gs.dgz;
     const int nops = bct->n_ops;
+    float t = 0.f;
+    if constexpr (MOV) {
+      typedef const float __attribute__((address_space(4)))* cfloat_p;  // written by an earlier launch only
+      t = ((cfloat_p)gs.times)[gs.s];
+    }
     for (int o = 0; o < nops; ++o) {
       const GridOp& op = bct->op[o];
       const float p0 = (float)i * g.dx, p1 = (float)j * g.dx, p2 = (float)k * g.dx;
@@ -589,6 +637,12 @@ __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int
       } else if (EXT && op.kind == 2) {
         if (!((gs.mask >> op.bit) & 1u)) continue;
         const float p[3] = {p0, p1, p2};
+        if constexpr (MOV) {
+          if (bct->mov[o].moving) {  // uniform
+            apply_mov(v, p, op, bct->ext[o], bct->mov[o], t);
+            continue;
+          }
+        }
         apply_ext(v, p, op, bct->ext[o]);
       } else {
         const float o0 = p0 - op.a[0], o1 = p1 - op.a[1], o2 = p2 - op.a[2];
@@ -671,11 +725,12 @@ __device__ __forceinline__ float4 node_sum(const float4* __restrict__ slots, int
   return a;
 }
 
-// EXT: node_update's (launch_grid picks it for a table with extended records)
-template <bool EXT>
+// EXT: node_update's (launch_grid picks it for a table with extended records);
+// GS = GridStepT: its MOV form, for a table with moving records
+template <bool EXT, class GS = GridStep>
 __global__ __launch_bounds__(512) void k_grid(GridDims g, Tiles tl, ChunkIn ck, const float4* __restrict__ slots,
                                               float4* __restrict__ gacc, float4* __restrict__ gvel,
-                                              const BcTable* __restrict__ bct, GridStep gs,
+                                              const BcTable* __restrict__ bct, GS gs,
                                               BinOut nb) {
   // housekeeping for the G2P that follows (stream order makes this safe)
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t <= tl.ntiles; t += gridDim.x * blockDim.x) {
@@ -1720,6 +1775,11 @@ struct gsmpm_mpm {
   BcTable* dev_bc = nullptr;
   int n_bc = 0;
   int n_ext = 0;  // extended collider records in host_bc: > 0 selects the EXT grid kernels (grid_ext)
+  int n_mov = 0;  // those of them that move (gsmpm_mpm_add_moving_collider): > 0 selects the MOV ones (grid_mov)
+  // the caller's clock of the current step call, one f32 per substep (gsmpm_mpm_step_timed): allocated with
+  // the first moving record, written by k_set_times in stream order before the substeps, read by the MOV kernels
+  float* times_dev = nullptr;
+  int times_cap = 0;
   bool has_particles = false;
   bool has_R = false;  // a gsmpm_mpm_postprocess ran since the particles were set (gsmpm_mpm_sh_rotations)
   hipStream_t cap = nullptr;
@@ -2260,9 +2320,23 @@ static int substep_begin(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream
 // (k_grid, k_grid_f); a table of fixed cubes and legacy planes runs the plain
 // ones, as k_fused_mixed / k_preprocess<true> are picked only for their scenes.
 static bool grid_ext(const gsmpm_mpm* h) { return h->n_ext > 0; }
+// Moving records select the MOV instantiation in the same way; ts is the
+// substep's entry of the table of caller times.
+static bool grid_mov(const gsmpm_mpm* h) { return h->n_mov > 0; }
+static GridStepT grid_step_t(const gsmpm_mpm* h, const GridStep& gs, int ts) {
+  GridStepT g;
+  static_cast<GridStep&>(g) = gs;
+  g.times = h->times_dev;
+  g.s = ts;
+  return g;
+}
 
-static void launch_grid(gsmpm_mpm* h, int c, const GridStep& gs, hipStream_t st, const hipEvent_t* ev) {
-  if (grid_ext(h))
+static void launch_grid(gsmpm_mpm* h, int c, const GridStep& gs, hipStream_t st, const hipEvent_t* ev, int ts = 0) {
+  if (grid_mov(h))
+    launch(ev, k_grid<true, GridStepT>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
+           (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_t(h, gs, ts),
+           bin_out(h, c ^ 1));
+  else if (grid_ext(h))
     launch(ev, k_grid<true>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
            (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, gs, bin_out(h, c ^ 1));
   else
@@ -2271,9 +2345,9 @@ static void launch_grid(gsmpm_mpm* h, int c, const GridStep& gs, hipStream_t st,
 }
 
 // Second half: grid update, G2P, binning of parity nx.
-static int substep_end(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream_t st, const hipEvent_t* e8) {
+static int substep_end(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream_t st, const hipEvent_t* e8, int ts) {
   const int nx = c ^ 1;
-  launch_grid(h, c, grid_step(h, dt, mask), st, e8 ? e8 + 2 : nullptr);
+  launch_grid(h, c, grid_step(h, dt, mask), st, e8 ? e8 + 2 : nullptr, ts);
   GSMPM_LAUNCH_CHECK();
   launch(e8 ? e8 + 4 : nullptr, k_g2p, dim3(g2p_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl,
          chunk_in(h, c), bin_out(h, nx), (const float4*)h->gvel, dt);
@@ -2287,7 +2361,7 @@ static int launch_substeps(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc,
     const uint32_t mask = bc ? bc[s] : 0xffffffffu;
     const hipEvent_t* e8 = ev ? ev + 8 * s : nullptr;
     int rc = substep_begin(h, dt, mask, parity, st, e8);
-    if (!rc) rc = substep_end(h, dt, mask, parity, st, e8);
+    if (!rc) rc = substep_end(h, dt, mask, parity, st, e8, s);
     if (rc) return rc;
     parity ^= 1;
   }
@@ -2456,13 +2530,17 @@ static GridBufs fold_grid_bufs(gsmpm_mpm* h, int wp, int r) {
   return GridBufs{fold_slots(h, r), fold_tbox(h, wp, r), fold_gacc(h, r), fold_flag(h, r), fold_scratch(h)};
 }
 static int launch_grid_f(gsmpm_mpm* h, int wp, float dt, uint32_t mask, const GridBufs& gb, int* zc, int* zf,
-                         hipStream_t st, const hipEvent_t* ev, const SlabWin* swp = nullptr) {
+                         hipStream_t st, const hipEvent_t* ev, const SlabWin* swp = nullptr, int ts = 0) {
   const SlabWin sw = swp ? *swp : SlabWin{};
   // a multiple of 8 workgroups: grid_work's XCD grouping takes b % 8 as the XCD
   const dim3 grid((std::min(kGridParts * h->ftl.ntiles, 1024 * kGridParts) + 7) / 8 * 8);
   if (swp)
     launch(ev, k_grid_f<true>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots, gb.gacc,
            h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
+  else if (grid_mov(h))
+    launch(ev, k_grid_f<false, true, GridStepT>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox,
+           gb.slots, gb.gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_t(h, grid_step(h, dt, mask), ts),
+           gb.esc_in, gb.esc_clear, zc, zf, sw);
   else if (grid_ext(h))
     launch(ev, k_grid_f<false, true>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots,
            gb.gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
@@ -2473,8 +2551,8 @@ static int launch_grid_f(gsmpm_mpm* h, int wp, float dt, uint32_t mask, const Gr
   return GSMPM_OK;
 }
 static int launch_grid_f(gsmpm_mpm* h, int wp, float dt, uint32_t mask, int ep, int* zc, int* zf, hipStream_t st,
-                         const hipEvent_t* ev, const SlabWin* swp = nullptr) {
-  return launch_grid_f(h, wp, dt, mask, grid_bufs(h, wp, ep), zc, zf, st, ev, swp);
+                         const hipEvent_t* ev, const SlabWin* swp = nullptr, int ts = 0) {
+  return launch_grid_f(h, wp, dt, mask, grid_bufs(h, wp, ep), zc, zf, st, ev, swp, ts);
 }
 
 // nsub substeps = nsub + 1 k_fused launches (P2G, nsub - 1 x G2P+P2G, G2P)
@@ -2548,7 +2626,7 @@ static int launch_substeps_f(gsmpm_mpm* h, float dt, int nsub, const uint32_t* b
       }
       rc = h->slab ? slab_grid_phase(h, wp, dt, mask, ep, zc, zf, st, xp)
                    : launch_grid_f(h, wp, dt, mask, fold ? fold_grid_bufs(h, wp, s) : grid_bufs(h, wp, ep), zc, zf, st,
-                                   e8 ? e8 + 2 : nullptr);
+                                   e8 ? e8 + 2 : nullptr, nullptr, s);
       if (rc) return rc;
       if (!fold) ep ^= 1;
       grid_at[s] = 1;
@@ -2589,6 +2667,41 @@ static void drop_graphs(gsmpm_mpm* h) {
 static int upload_bc(gsmpm_mpm* h) {
   GSMPM_HIP(hipMemcpy(h->dev_bc, &h->host_bc, sizeof(BcTable), hipMemcpyHostToDevice));
   drop_graphs(h);
+  return GSMPM_OK;
+}
+
+// The caller's clock of one step call on the device: n f32 values into
+// times_dev[0..n), kTimeBatch per one-workgroup launch, the values travelling
+// as launch arguments.  The launches are ordered on `st` like the substeps
+// they precede, so step calls queued back to back need no host sync: the
+// next call's values are written after this call's last grid kernel read
+// its own.  time == nullptr: zeros (gsmpm_mpm_time_kernels, _profile_substeps).
+// The table (16 KiB at first) grows by doubling; growing frees the old one,
+// which waits for the device, and drops the graphs that baked its address.
+constexpr int kTimeBatch = 256;
+struct TimeBatch {
+  float t[kTimeBatch];
+};
+__global__ __launch_bounds__(kTimeBatch) void k_set_times(float* __restrict__ table, int n, TimeBatch b) {
+  if ((int)threadIdx.x < n) table[threadIdx.x] = b.t[threadIdx.x];
+}
+static int upload_times(gsmpm_mpm* h, const double* time, int n, hipStream_t st) {
+  if (n > h->times_cap) {
+    int cap = std::max(h->times_cap, 4096);
+    while (cap < n) cap *= 2;
+    drop_graphs(h);
+    release(h, &h->times_dev);
+    h->times_cap = 0;
+    GSMPM_HIP(alloc(h, &h->times_dev, (size_t)cap, kMemCommon, kFillZero));
+    h->times_cap = cap;
+  }
+  for (int s0 = 0; s0 < n; s0 += kTimeBatch) {
+    TimeBatch b;
+    const int m = std::min(kTimeBatch, n - s0);
+    for (int i = 0; i < kTimeBatch; ++i) b.t[i] = i < m && time ? (float)time[s0 + i] : 0.f;
+    hipLaunchKernelGGL(k_set_times, dim3(1), dim3(kTimeBatch), 0, st, h->times_dev + s0, m, b);
+    GSMPM_LAUNCH_CHECK();
+  }
   return GSMPM_OK;
 }
 
@@ -3138,8 +3251,8 @@ int gsmpm_mpm_add_plane_collider(gsmpm_mpm* h, const double p[3], const double n
 // arguments of solver.py:140-147).  Refused, with nothing changed, where no
 // EXT grid update exists: a slab's grid pass (slab.h) and the folded staging
 // of k_fused (GSMPM_FOLD=1) apply the plain node_update.
-int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* c) {
-  GSMPM_REQUIRE(h && c, "gsmpm_mpm_add_collider: null argument");
+// mv: the record's motion (gsmpm_mpm_add_moving_collider), nullptr for a static one
+static int add_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_collider_motion* mv) {
   if (h->slab) {
     set_error("gsmpm_mpm_add_collider: extended colliders are not supported on a slab of a multi-GPU domain "
               "(its grid passes apply fixed cubes and plane colliders only)");
@@ -3180,8 +3293,33 @@ int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* c) {
   op.friction = (float)c->friction;
   h->host_bc.ext[o] = GridOpExt{c->shape, c->surface, (float)c->damping};
   ++h->n_ext;
+  h->host_bc.mov[o] = GridOpMov{};
+  if (mv) {
+    h->host_bc.mov[o] = GridOpMov{{(float)mv->velocity[0], (float)mv->velocity[1], (float)mv->velocity[2]},
+                                  (float)mv->t_start, (float)mv->t_end, 1};
+    ++h->n_mov;
+    const int rt = upload_times(h, nullptr, 1, nullptr);  // the table exists, and reads t = 0 until a timed step
+    if (rt) return rt;
+  }
   int rc = upload_bc(h);
   return rc ? rc : id;
+}
+
+int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* c) {
+  GSMPM_REQUIRE(h && c, "gsmpm_mpm_add_collider: null argument");
+  return add_collider(h, c, nullptr);
+}
+
+// A moving record: the same record plus a velocity and a motion window on the
+// caller's clock.  Refused wherever gsmpm_mpm_add_collider is, in its words.
+int gsmpm_mpm_add_moving_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_collider_motion* mv) {
+  GSMPM_REQUIRE(h && c && mv, "gsmpm_mpm_add_moving_collider: null argument");
+  GSMPM_REQUIRE(std::isfinite(mv->velocity[0]) && std::isfinite(mv->velocity[1]) && std::isfinite(mv->velocity[2]),
+                "gsmpm_mpm_add_moving_collider: non-finite velocity");
+  GSMPM_REQUIRE(std::isfinite(mv->t_start), "gsmpm_mpm_add_moving_collider: non-finite t_start");
+  GSMPM_REQUIRE(!std::isnan(mv->t_end), "gsmpm_mpm_add_moving_collider: t_end is NaN");
+  GSMPM_REQUIRE(mv->t_end >= mv->t_start, "gsmpm_mpm_add_moving_collider: t_end < t_start");
+  return add_collider(h, c, mv);
 }
 
 namespace gsmpm {
@@ -3210,8 +3348,10 @@ static void choose_rebins(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc) 
 }
 }  // namespace gsmpm
 
-int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, void* stream) {
-  GSMPM_REQUIRE(h, "gsmpm_mpm_step: null handle");
+// gsmpm_mpm_step and gsmpm_mpm_step_timed: `time` (one caller-clock value per
+// substep) is uploaded first on a handle that holds moving records, and is
+// ignored on any other, which then runs exactly what gsmpm_mpm_step runs.
+static int step_impl(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, const double* time, void* stream) {
   if (!h->has_particles) {
     set_error("gsmpm_mpm_step: particles not set");
     return GSMPM_ESTATE;
@@ -3238,6 +3378,10 @@ int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, voi
   if (use_fused(h)) choose_rebins(h, dt, nsub, bc);
   const bool use_graph = !(h->prm.flags & GSMPM_FLAG_NO_GRAPH) && nsub >= 2;
   int rc;
+  if (grid_mov(h)) {
+    rc = upload_times(h, time, nsub, st);
+    if (rc) return rc;
+  }
   if (!use_graph) {
     int parity = h->cur_box;
     rc = use_fused(h) ? launch_substeps_f(h, dt, nsub, bc, st, h->fbpar, h->fep)
@@ -3250,6 +3394,28 @@ int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, voi
   if (!rc && use_fused(h) && h->fu.vmax_host && h->rebin_auto)
     GSMPM_HIP(hipMemcpyAsync(h->fu.vmax_host, h->fu.vmax_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   return rc;
+}
+
+int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, void* stream) {
+  GSMPM_REQUIRE(h, "gsmpm_mpm_step: null handle");
+  if (grid_mov(h)) {
+    set_error("gsmpm_mpm_step: the handle holds moving colliders (gsmpm_mpm_add_moving_collider), whose placement "
+              "depends on the caller's clock; step it with gsmpm_mpm_step_timed");
+    return GSMPM_ESTATE;
+  }
+  return step_impl(h, dt, nsub, bc, nullptr, stream);
+}
+
+int gsmpm_mpm_step_timed(gsmpm_mpm* h, float dt, int32_t nsub, const uint32_t* bc, const double* time, void* stream) {
+  GSMPM_REQUIRE(h, "gsmpm_mpm_step_timed: null handle");
+  GSMPM_REQUIRE(time, "gsmpm_mpm_step_timed: null time");
+  for (int s = 0; s < nsub; ++s) GSMPM_REQUIRE(std::isfinite(time[s]), "gsmpm_mpm_step_timed: non-finite time");
+  return step_impl(h, dt, nsub, bc, time, stream);
+}
+
+int gsmpm_mpm_graph_count(gsmpm_mpm* h) {
+  GSMPM_REQUIRE(h, "gsmpm_mpm_graph_count: null handle");
+  return (int)h->graphs.size();
 }
 
 int gsmpm_mpm_check_finite(gsmpm_mpm* h, int32_t clear, void* stream) {
@@ -3494,6 +3660,10 @@ int gsmpm_mpm_profile_substeps(gsmpm_mpm* h, float dt, int32_t nsub, const uint3
   hipStream_t st = (hipStream_t)stream;
   for (int k = 0; k < 4; ++k) kernel_ms[k] = 0.f;
   if (nsub == 0) return GSMPM_OK;
+  if (grid_mov(h)) {  // moving records stand at t = 0
+    const int rt = upload_times(h, nullptr, nsub, st);
+    if (rt) return rt;
+  }
   if (use_fused(h)) {
     std::vector<hipEvent_t> ev(8 * (size_t)(nsub + 1));
     for (auto& e : ev) GSMPM_HIP(hipEventCreate(&e));
@@ -3563,6 +3733,10 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
   const size_t pbytes = sizeof(float) * (size_t)NPLANES * h->np;
   if (!h->planes_tmp) GSMPM_HIP(alloc(h, &h->planes_tmp, (size_t)NPLANES * h->np, kMemCommon));
   GSMPM_HIP(hipMemcpyAsync(h->planes_tmp, h->planes, pbytes, hipMemcpyDeviceToDevice, st));
+  if (grid_mov(h)) {  // moving records stand at t = 0 (every grid launch here reads entry 0)
+    const int rt = upload_times(h, nullptr, 1, st);
+    if (rt) return rt;
+  }
   if (use_fused(h)) return time_kernels_f(h, dt, bc_active, reps, ms4, st, pbytes);
   const int c = h->cur_box, nx = c ^ 1;
   const GridStep gs = grid_step(h, dt, bc_active);

@@ -64,11 +64,21 @@ struct GridOpExt {
   int shape, surface;
   float damping;
 };
+// The motion of a moving record (gsmpm_mpm_add_moving_collider): velocity w
+// and motion window [t0, t1) on the caller's clock, f32 of the caller's
+// doubles.  moving = 0: a static record (gsmpm_mpm_add_collider) in a table
+// that holds a moving one; the MOV instantiations then run apply_ext as the
+// EXT ones do.
+struct GridOpMov {
+  float w[3], t0, t1;
+  int moving;
+};
 struct BcTable {
   int n_imp, n_ops;
   Impulse imp[kMaxBC];
   GridOp op[kMaxBC];
   GridOpExt ext[kMaxBC];  // parallel to op[], after it: the offsets the plain instantiations read do not move
+  GridOpMov mov[kMaxBC];  // parallel again, after ext[]: read by the MOV instantiations only
 };
 
 #ifndef GSMPM_PSTORE

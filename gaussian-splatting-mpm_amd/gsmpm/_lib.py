@@ -48,6 +48,11 @@ class Collider(ctypes.Structure):
     ]
 
 
+class ColliderMotion(ctypes.Structure):
+    """gsmpm_collider_motion (include/gsmpm.h)."""
+    _fields_ = [("velocity", ctypes.c_double * 3), ("t_start", ctypes.c_double), ("t_end", ctypes.c_double)]
+
+
 class RasterArgs(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32), ("D", ctypes.c_int32), ("M", ctypes.c_int32),
@@ -88,8 +93,13 @@ _SIGS = {
     "gsmpm_mpm_add_plane_collider": (ctypes.c_int, [c_void_p, ctypes.c_double * 3, ctypes.c_double * 3,
                                                     ctypes.c_double]),
     "gsmpm_mpm_add_collider": (ctypes.c_int, [c_void_p, ctypes.POINTER(Collider)]),
+    "gsmpm_mpm_add_moving_collider": (ctypes.c_int, [c_void_p, ctypes.POINTER(Collider),
+                                                     ctypes.POINTER(ColliderMotion)]),
     "gsmpm_mpm_step": (ctypes.c_int, [c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32),
                                       c_void_p]),
+    "gsmpm_mpm_step_timed": (ctypes.c_int, [c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32),
+                                            ctypes.POINTER(ctypes.c_double), c_void_p]),
+    "gsmpm_mpm_graph_count": (ctypes.c_int, [c_void_p]),
     "gsmpm_rccl_unique_id": (ctypes.c_int, [c_void_p]),
     "gsmpm_rccl_comm_init": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void_p)]),
     "gsmpm_rccl_comm_destroy": (ctypes.c_int, [c_void_p]),

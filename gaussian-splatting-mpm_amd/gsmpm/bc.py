@@ -60,3 +60,16 @@ def substep_masks(specs, time: float, dt: float, n: int):
         masks.append(m)
         t += dt
     return masks, t
+
+
+def substep_times(time: float, dt: float, n: int):
+    """The clock of ``substep_masks`` at each of n substeps starting at host
+    time ``time``: the same float64 additions in the same order, for
+    ``Simulator.step(dt, masks, times)`` (moving colliders).  Returns
+    (times, time_after)."""
+    times = []
+    t = time
+    for _ in range(n):
+        times.append(t)
+        t += dt
+    return times, t

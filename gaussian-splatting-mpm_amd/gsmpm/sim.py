@@ -87,12 +87,19 @@ class Simulator:
                      "add_plane_collider")
 
     def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, *, point=None, normal=None,
-                     center=None, radius=None, half=None) -> int:
+                     center=None, radius=None, half=None, velocity=None, move_start=None, move_end=None) -> int:
         """An extended collider (gsmpm_mpm_add_collider; no reference counterpart):
         ``shape`` "plane" (point, normal), "ball" (center, radius), "box" or
         "walls" (center, half: a solid box / everything outside it), ``surface``
         "sticky", "slip" or "separate".  Returns its bit of the activity mask,
-        which -- unlike the legacy plane collider's -- it honours."""
+        which -- unlike the legacy plane collider's -- it honours.
+
+        ``velocity`` (three components) makes it a moving record
+        (gsmpm_mpm_add_moving_collider): it translates with that velocity
+        while move_start <= time < move_end (defaults 0 and +inf) on the
+        clock the caller hands ``step`` as ``times``, stands at its placement
+        before and where it arrived after, and acts on the velocity relative
+        to its own."""
         if shape not in _lib.SHAPE:
             raise ValueError(f"add_collider: unknown shape {shape!r} (one of {sorted(_lib.SHAPE)})")
         if surface not in _lib.SURFACE:
@@ -109,7 +116,19 @@ class Simulator:
         c.a[:] = [float(a) for a in given[want[0]]]
         c.b[:] = [float(radius), 0.0, 0.0] if shape == "ball" else [float(a) for a in given[want[1]]]
         c.friction, c.damping = float(friction), float(damping)
-        return check(LIB.gsmpm_mpm_add_collider(self._h, ctypes.byref(c)), "add_collider")
+        if velocity is None:
+            if move_start is not None or move_end is not None:
+                raise TypeError("add_collider: move_start / move_end need a velocity")
+            return check(LIB.gsmpm_mpm_add_collider(self._h, ctypes.byref(c)), "add_collider")
+        m = _lib.ColliderMotion()
+        m.velocity[:] = [float(a) for a in velocity]
+        m.t_start = 0.0 if move_start is None else float(move_start)
+        m.t_end = float("inf") if move_end is None else float(move_end)
+        return check(LIB.gsmpm_mpm_add_moving_collider(self._h, ctypes.byref(c), ctypes.byref(m)), "add_collider")
+
+    def graph_count(self) -> int:
+        """Step graphs the handle caches now (gsmpm_mpm_graph_count; diagnostics)."""
+        return check(LIB.gsmpm_mpm_graph_count(self._h), "graph_count")
 
     # ------------------------------------------------ per-particle materials --
     @property
@@ -137,12 +156,23 @@ class Simulator:
                                               float(mu), stream_of(self.device)), "gsmpm_mpm_set_region_params")
 
     # ------------------------------------------------------------ stepping --
-    def step(self, dt: float, masks):
+    def step(self, dt: float, masks, times=None):
+        """len(masks) substeps.  ``times``: the caller's float64 clock at each
+        substep (bc.substep_times), required once the simulator holds a moving
+        collider -- the library then refuses the untimed call (RuntimeError)
+        -- and ignored otherwise (gsmpm_mpm_step_timed)."""
         n = len(masks)
         if n == 0:
             return
         arr = (ctypes.c_uint32 * n)(*[int(m) & 0xFFFFFFFF for m in masks])
-        check(LIB.gsmpm_mpm_step(self._h, ctypes.c_float(dt), n, arr, stream_of(self.device)), "gsmpm_mpm_step")
+        if times is None:
+            check(LIB.gsmpm_mpm_step(self._h, ctypes.c_float(dt), n, arr, stream_of(self.device)), "gsmpm_mpm_step")
+            return
+        if len(times) != n:
+            raise ValueError(f"step: {n} masks but {len(times)} times")
+        tarr = (ctypes.c_double * n)(*[float(t) for t in times])
+        check(LIB.gsmpm_mpm_step_timed(self._h, ctypes.c_float(dt), n, arr, tarr, stream_of(self.device)),
+              "gsmpm_mpm_step_timed")
 
     def check_finite(self, clear: bool = False):
         """SURVEY 5's per-frame NaN / Inf check: waits for the stream and

@@ -139,7 +139,9 @@ class ColliderBC:
     "separate", friction, damping -- active while start_time <= time <
     end_time on the host's float64 clock.  The per-node work runs in the EXT
     grid kernels (gsmpm_mpm_add_collider).  isCollide stays False: unlike the
-    legacy plane collider this one honours its window."""
+    legacy plane collider this one honours its window.  With a ``velocity``
+    it is a moving record (gsmpm_mpm_add_moving_collider): it translates while
+    move_start <= time < move_end (defaults: start_time, end_time)."""
 
     _geometry = {"plane": ("point", "normal"), "ball": ("center", "radius"), "box": ("center", "half"),
                  "walls": ("center", "half")}
@@ -157,6 +159,17 @@ class ColliderBC:
         self.start_time = float(bc_args.get("start_time", 0.0))
         self.end_time = float(bc_args.get("end_time", 999.0))
         self.geometry = {k: bc_args[k] for k in self._geometry[self.shape]}  # KeyError names the missing one
+        # a moving record: velocity, and the window of the motion (default: the activity window)
+        self.velocity = bc_args.get("velocity")
+        self.motion = {}
+        if self.velocity is not None:
+            ms, me = bc_args.get("move_start"), bc_args.get("move_end")
+            self.move_start = self.start_time if ms is None else float(ms)
+            self.move_end = self.end_time if me is None else float(me)
+            self.motion = dict(velocity=[float(a) for a in self.velocity], move_start=self.move_start,
+                               move_end=self.move_end)
+        elif bc_args.get("move_start") is not None or bc_args.get("move_end") is not None:
+            raise TypeError("collider: move_start / move_end need a velocity")
         self.isCollide = False
         self.bit = None  # library bc id (bit of the activity mask)
 

@@ -37,6 +37,7 @@ class MPM_Simulator:
         self.grid_postprocess = []
         self.init_particles = []
         self._queue = []
+        self._queue_t = []  # the clock at each queued substep (moving colliders)
         self._queue_dt = None
         if self.fitting:  # MPM_state_opt (model.py:135-223) on gsmpm_fit_*
             self._sim = None
@@ -84,6 +85,7 @@ class MPM_Simulator:
             self.flush()
         self._queue_dt = dt
         self._queue.append(self._mask_now())
+        self._queue_t.append(self.time)
         self.time += dt  # float64 host clock, solver.py:52
         if len(self._queue) >= _MAX_QUEUE:
             self.flush()
@@ -93,7 +95,8 @@ class MPM_Simulator:
             return
         if self._queue:
             q, self._queue = self._queue, []
-            self._sim.step(float(self._queue_dt), q)
+            t, self._queue_t = self._queue_t, []
+            self._sim.step(float(self._queue_dt), q, t)
 
     def postprocess(self):
         """compute_cov_from_F + compute_R_from_F (solver.py:135-137)."""
@@ -164,26 +167,29 @@ class MPM_Simulator:
         self.grid_postprocess.append(cl)
 
     def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, start_time=0.0, end_time=999.0,
-                     **geometry):
+                     velocity=None, move_start=None, move_end=None, **geometry):
         """An extended collider (not in the reference; add_surface_collider above
         stays the legacy plane): ``shape`` "plane" (point=, normal=), "ball"
         (center=, radius=), "box" or "walls" (center=, half=); ``surface``
         "sticky", "slip" or "separate"; active on the substeps where
         start_time <= time < end_time.  Returns the descriptor (its ``bit`` is
         the library's bc id).  Same record as a ``{"type": "collider", ...}``
-        entry of set_boundary_conditions."""
+        entry of set_boundary_conditions.  ``velocity`` makes it a moving
+        record: it translates while move_start <= time < move_end (defaults:
+        start_time, end_time) on the same clock, whether active or not."""
         if self.fitting:
             raise TypeError("add_collider applies to the forward-only simulator; the fitting path (MPM_state_opt) "
                             "has no extended colliders")
         bc = ColliderBC(self.n_particles, dict(geometry, type="collider", shape=shape, surface=surface,
                                                friction=friction, damping=damping, start_time=start_time,
-                                               end_time=end_time))
+                                               end_time=end_time, velocity=velocity, move_start=move_start,
+                                               move_end=move_end))
         self._add_collider_bc(bc)
         return bc
 
     def _add_collider_bc(self, bc):
         self.flush()  # substeps queued so far ran without it
-        bc.bit = self._sim.add_collider(bc.shape, bc.surface, bc.friction, bc.damping, **bc.geometry)
+        bc.bit = self._sim.add_collider(bc.shape, bc.surface, bc.friction, bc.damping, **bc.geometry, **bc.motion)
         self.grid_postprocess.append(bc)
 
     # ------------------------------------------- differentiable (fitting) --

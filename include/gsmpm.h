@@ -142,6 +142,56 @@ int gsmpm_mpm_add_collider(gsmpm_mpm* h, const gsmpm_collider* collider);
  * read here without a sync: the error surfaces at the call after the frame
  * that produced it, or at gsmpm_mpm_check_finite). */
 int gsmpm_mpm_step(gsmpm_mpm* h, float dt, int32_t n_substeps, const uint32_t* bc_active, void* stream);
+
+/* Moving colliders: an extended collider record (above, unchanged) that
+ * translates.  No reference counterpart; the semantics are this library's
+ * (DESIGN.md "Moving colliders").  The motion is a velocity w and a motion
+ * window [t_start, t_end) on the caller's clock, all four stored as f32 of the
+ * doubles given; t_end may be +inf.  The library keeps no clock: the caller
+ * hands gsmpm_mpm_step_timed, for each substep, the time at which it decided
+ * that substep's bc_active word.  On a substep whose time reads t (f32 of the
+ * double), in f32, unfused, left to right, with t0 = t_start, t1 = t_end:
+ *   tc = fminf(fmaxf(t, t0), t1)     tau = tc - t0
+ *   c  = a + w tau                   (point of a plane, centre of ball / box / walls)
+ *   wc = (t >= t0 && t < t1) ? w : 0 (the collider's velocity now)
+ * so the record stands at a before t0, translates inside the window and
+ * stands where it arrived from t1 on.  The inside test and the normal are
+ * gsmpm_mpm_add_collider's with c in place of a (a plane keeps its normal).
+ * On a node the record hits, the response acts on the relative velocity:
+ *   u = v - wc;  u = response(u) (sticky u = 0; WALLS once per violated axis;
+ *   damping on u as above on v);  v = u + wc.
+ * A node it does not hit keeps v bit for bit.  The record's bit of bc_active
+ * means what it does for a static record: an inactive record is skipped, and
+ * its clock still runs (a record switched on halfway through its motion
+ * window appears halfway along).  An all-zero velocity is legal and still
+ * makes a moving record.
+ * Returns the bc id, or GSMPM_EINVAL: everything gsmpm_mpm_add_collider
+ * refuses, a non-finite velocity, a non-finite t_start, t_end NaN, t_end <
+ * t_start.  GSMPM_ESTATE as gsmpm_mpm_add_collider: a slab handle (and
+ * gsmpm_mpm_slab_init refuses a handle that holds such a record), a handle
+ * created with GSMPM_FOLD=1.  The first moving record switches the handle to
+ * the MOV instantiations of the grid kernels; a static extended record in
+ * such a table gives what the EXT ones give (==). */
+typedef struct {
+  double velocity[3];     /* w */
+  double t_start, t_end;  /* motion window [t_start, t_end) on the caller's clock */
+} gsmpm_collider_motion;
+int gsmpm_mpm_add_moving_collider(gsmpm_mpm* h, const gsmpm_collider* collider, const gsmpm_collider_motion* motion);
+/* gsmpm_mpm_step with the caller's clock: time[s] is the clock at substep s
+ * (the value it had when bc_active[s] was decided).  The times go to a small
+ * device table (one f32 per substep, written on `stream` before the substeps,
+ * with no host synchronisation; calls may be queued back to back), and the
+ * grid kernel of substep s reads entry s: the cached step graphs do not
+ * depend on time.  GSMPM_EINVAL: NULL time, a non-finite entry.  On a handle
+ * without moving records it is gsmpm_mpm_step: the times are ignored, the
+ * same kernels and graphs run, the results are bit-equal.  gsmpm_mpm_step on
+ * a handle that holds a moving record returns GSMPM_ESTATE and launches
+ * nothing; gsmpm_mpm_time_kernels and gsmpm_mpm_profile_substeps run such a
+ * handle at t = 0. */
+int gsmpm_mpm_step_timed(gsmpm_mpm* h, float dt, int32_t n_substeps, const uint32_t* bc_active, const double* time,
+                         void* stream);
+/* The step graphs the handle caches now (diagnostics). */
+int gsmpm_mpm_graph_count(gsmpm_mpm* h);
 /* Synchronizes `stream`, then GSMPM_ESTATE if any substep so far produced a
  * non-finite particle state (position, mass, velocity, C or stress; clear
  * != 0 resets the word; set_particles does too), else GSMPM_OK.  No
