@@ -500,6 +500,14 @@ struct GridStepT : GridStep {
   const float* times;
   int s;
 };
+// The step argument of the ROT instantiations (tables with a rotating record,
+// gsmpm_mpm_add_rotating_collider): GridStepT plus the pose table, written by
+// k_set_poses in stream order after the times and before the call's substeps.
+// The pose of substep s and rotating record j is poses[s * n_rot + j].
+struct GridStepR : GridStepT {
+  const float* poses;
+  int n_rot;
+};
 
 // Extended collider records (kind 2: plane, ball, box or walls with a sticky
 // / slip / separate surface, a damping factor and an activity bit; gsmpm.h
@@ -598,6 +606,41 @@ __device__ __forceinline__ void apply_mov(float (&v)[3], const float (&p)[3], co
   }
 }
 
+// One rotating record at caller time t (DESIGN.md "Rotating colliders"), its
+// pose {R[9], c[3], o[3]} of this substep read from the pose table: the node
+// and the velocity relative to the collider's at the node go to the body
+// frame, the record acts there as it stands (apply_ext_at on the offset d,
+// which is its p - c with c = 0: d - 0 is d, bit for bit), and a node it hit
+// is rotated back.  f32, unfused, left to right, sums in index order.
+typedef const float __attribute__((address_space(4)))* cfloat_p;  // uniform words written by an earlier launch only
+__device__ __forceinline__ void apply_rot(float (&v)[3], const float (&p)[3], const GridOp& op, const GridOpExt& ex,
+                                          const GridOpMov& mv, const GridOpRot& rt, cfloat_p pose, float t) {
+  const bool mov = t >= mv.t0 && t < mv.t1;
+  float R[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) R[e] = pose[e];
+  const float q[3] = {p[0] - pose[9], p[1] - pose[10], p[2] - pose[11]};
+  const float r[3] = {p[0] - pose[12], p[1] - pose[13], p[2] - pose[14]};
+  const float x[3] = {rt.om[1] * r[2] - rt.om[2] * r[1], rt.om[2] * r[0] - rt.om[0] * r[2],
+                      rt.om[0] * r[1] - rt.om[1] * r[0]};
+  float d[3], wc[3], s[3], u[3];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    wc[e] = mov ? mv.w[e] + x[e] : 0.0f;
+    s[e] = v[e] - wc[e];
+  }
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    d[e] = R[e] * q[0] + R[3 + e] * q[1] + R[6 + e] * q[2];
+    u[e] = R[e] * s[0] + R[3 + e] * s[1] + R[6 + e] * s[2];
+  }
+  const float zero[3] = {0.f, 0.f, 0.f};
+  if (apply_ext_at(u, d, zero, op, ex)) {
+#pragma unroll
+    for (int e = 0; e < 3; ++e) v[e] = (R[3 * e] * u[0] + R[3 * e + 1] * u[1] + R[3 * e + 2] * u[2]) + wc[e];
+  }
+}
+
 // grid_normalization_and_gravity (utils.py:177-183) and the grid_postprocess
 // list (solver.py:41-46) of one node: BasicBC.apply (boundary_conditions.py:
 // 23-27) / MPM_Collider.collide (collider.py:13-44), pointwise, in list order.
@@ -608,10 +651,13 @@ __device__ __forceinline__ void apply_mov(float (&v)[3], const float (&p)[3], co
 // (grid_mov); the substep's time is one uniform word of the caller's table,
 // read through the constant address space so that it is a scalar load issued
 // with the table's.
+// GS = GridStepR (ROT): the table may hold rotating records too (grid_rot);
+// their poses are uniform words of the pose table, read in the same way.
 template <bool EXT = false, class GS = GridStep>
 __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int k, const GridDims& g,
                                               const GS& gs, const BcTable* __restrict__ bct) {
-  constexpr bool MOV = std::is_same<GS, GridStepT>::value;
+  constexpr bool ROT = std::is_same<GS, GridStepR>::value;
+  constexpr bool MOV = ROT || std::is_same<GS, GridStepT>::value;
   static_assert(!MOV || EXT, "moving records are extended records");
   float v[3] = {0.f, 0.f, 0.f};
   if (a.w > 1e-15f) {
@@ -620,10 +666,7 @@ __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int
     v[2] = a.z / a.w + gs.dgz;
     const int nops = bct->n_ops;
     float t = 0.f;
-    if constexpr (MOV) {
-      typedef const float __attribute__((address_space(4)))* cfloat_p;  // written by an earlier launch only
-      t = ((cfloat_p)gs.times)[gs.s];
-    }
+    if constexpr (MOV) t = ((cfloat_p)gs.times)[gs.s];  // written by an earlier launch only
     for (int o = 0; o < nops; ++o) {
       const GridOp& op = bct->op[o];
       const float p0 = (float)i * g.dx, p1 = (float)j * g.dx, p2 = (float)k * g.dx;
@@ -637,6 +680,14 @@ __device__ __forceinline__ float4 node_update(const float4& a, int i, int j, int
       } else if (EXT && op.kind == 2) {
         if (!((gs.mask >> op.bit) & 1u)) continue;
         const float p[3] = {p0, p1, p2};
+        if constexpr (ROT) {
+          const int jr = bct->rot[o].idx;
+          if (jr >= 0) {  // uniform
+            apply_rot(v, p, op, bct->ext[o], bct->mov[o], bct->rot[o],
+                      (cfloat_p)gs.poses + (size_t)(gs.s * gs.n_rot + jr) * kPoseFloats, t);
+            continue;
+          }
+        }
         if constexpr (MOV) {
           if (bct->mov[o].moving) {  // uniform
             apply_mov(v, p, op, bct->ext[o], bct->mov[o], t);
@@ -1780,6 +1831,15 @@ struct gsmpm_mpm {
   // the first moving record, written by k_set_times in stream order before the substeps, read by the MOV kernels
   float* times_dev = nullptr;
   int times_cap = 0;
+  // those of the moving records that rotate (gsmpm_mpm_add_rotating_collider): > 0 selects the ROT grid kernels
+  // (grid_rot).  rot_dev: their RotRec, in table order; poses_dev: kPoseFloats per substep and rotating record of
+  // the current step call, [times_cap][poses_rot], written by k_set_poses after k_set_times; poses_n: the
+  // substeps of the last fill (gsmpm_mpm_get_poses)
+  int n_rot = 0;
+  RotRec host_rot[kMaxBC] = {};
+  RotRec* rot_dev = nullptr;
+  float* poses_dev = nullptr;
+  int poses_rot = 0, poses_n = 0;
   bool has_particles = false;
   bool has_R = false;  // a gsmpm_mpm_postprocess ran since the particles were set (gsmpm_mpm_sh_rotations)
   hipStream_t cap = nullptr;
@@ -2330,9 +2390,22 @@ static GridStepT grid_step_t(const gsmpm_mpm* h, const GridStep& gs, int ts) {
   g.s = ts;
   return g;
 }
+// Rotating records select the ROT instantiation, which reads the pose table too.
+static bool grid_rot(const gsmpm_mpm* h) { return h->n_rot > 0; }
+static GridStepR grid_step_r(const gsmpm_mpm* h, const GridStep& gs, int ts) {
+  GridStepR g;
+  static_cast<GridStepT&>(g) = grid_step_t(h, gs, ts);
+  g.poses = h->poses_dev;
+  g.n_rot = h->poses_rot;
+  return g;
+}
 
 static void launch_grid(gsmpm_mpm* h, int c, const GridStep& gs, hipStream_t st, const hipEvent_t* ev, int ts = 0) {
-  if (grid_mov(h))
+  if (grid_rot(h))
+    launch(ev, k_grid<true, GridStepR>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
+           (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_r(h, gs, ts),
+           bin_out(h, c ^ 1));
+  else if (grid_mov(h))
     launch(ev, k_grid<true, GridStepT>, dim3(grid_grid(h)), dim3(512), st, h->g, h->tl, chunk_in(h, c),
            (const float4*)h->ph.slots, h->gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_t(h, gs, ts),
            bin_out(h, c ^ 1));
@@ -2537,6 +2610,10 @@ static int launch_grid_f(gsmpm_mpm* h, int wp, float dt, uint32_t mask, const Gr
   if (swp)
     launch(ev, k_grid_f<true>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox, gb.slots, gb.gacc,
            h->gvel, (const BcTable*)h->dev_bc, grid_step(h, dt, mask), gb.esc_in, gb.esc_clear, zc, zf, sw);
+  else if (grid_rot(h))
+    launch(ev, k_grid_f<false, true, GridStepR>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox,
+           gb.slots, gb.gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_r(h, grid_step(h, dt, mask), ts),
+           gb.esc_in, gb.esc_clear, zc, zf, sw);
   else if (grid_mov(h))
     launch(ev, k_grid_f<false, true, GridStepT>, grid, dim3(kGridT), st, h->g, h->ftl, chunk_in_f(h, wp), gb.tbox,
            gb.slots, gb.gacc, h->gvel, (const BcTable*)h->dev_bc, grid_step_t(h, grid_step(h, dt, mask), ts),
@@ -2685,7 +2762,64 @@ struct TimeBatch {
 __global__ __launch_bounds__(kTimeBatch) void k_set_times(float* __restrict__ table, int n, TimeBatch b) {
   if ((int)threadIdx.x < n) table[threadIdx.x] = b.t[threadIdx.x];
 }
+// The poses of the rotating records on the n substeps whose times the launches
+// before it wrote (DESIGN.md "Rotating colliders"): one thread per (substep s,
+// rotating record j) writes {R[9], c[3], o[3], 0} to poses[s * n_rot + j].
+// The angle, its sine and cosine and Rodrigues' formula are f64, each entry
+// of R rounded to f32 once; o and c are f32, unfused, left to right.  The
+// grid kernels so read a pose and pay no trigonometry.
+__global__ __launch_bounds__(256) void k_set_poses(float* __restrict__ poses, const float* __restrict__ times,
+                                                   const RotRec* __restrict__ recs, int n, int n_rot) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * n_rot) return;
+  const RotRec rc = recs[i % n_rot];
+  const float t = times[i / n_rot];
+  const float tc = fminf(fmaxf(t, rc.t0), rc.t1);
+  const float tau = tc - rc.t0;
+  const double theta = rc.wm * (double)tau;
+  const double sn = sin(theta), vc = 1.0 - cos(theta);
+  const double K[9] = {0.0, -rc.k[2], rc.k[1], rc.k[2], 0.0, -rc.k[0], -rc.k[1], rc.k[0], 0.0};
+  float R[9];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const double kk = K[3 * a] * K[b] + K[3 * a + 1] * K[3 + b] + K[3 * a + 2] * K[6 + b];
+      R[3 * a + b] = (float)((a == b ? 1.0 : 0.0) + sn * K[3 * a + b] + vc * kk);
+    }
+  const float e[3] = {rc.a[0] - rc.piv[0], rc.a[1] - rc.piv[1], rc.a[2] - rc.piv[2]};
+  float* out = poses + (size_t)i * kPoseFloats;
+#pragma unroll
+  for (int a = 0; a < 9; ++a) out[a] = R[a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float o = rc.piv[a] + rc.w[a] * tau;
+    out[9 + a] = o + (R[3 * a] * e[0] + R[3 * a + 1] * e[1] + R[3 * a + 2] * e[2]);
+    out[12 + a] = o;
+  }
+  out[15] = 0.f;
+}
+// The pose table follows the times table: [times_cap][n_rot] poses, regrown
+// (and the graphs dropped) when either grows; filled on `st` right after the
+// times, by one launch for all n substeps of the call.
+static int set_poses(gsmpm_mpm* h, int n, bool grew, hipStream_t st) {
+  if (grew || h->poses_rot != h->n_rot) {
+    drop_graphs(h);
+    release(h, &h->poses_dev);
+    h->poses_rot = 0;
+    GSMPM_HIP(alloc(h, &h->poses_dev, (size_t)h->times_cap * h->n_rot * kPoseFloats, kMemCommon, kFillZero));
+    h->poses_rot = h->n_rot;
+  }
+  const int work = n * h->n_rot;
+  h->poses_n = n;
+  if (work == 0) return GSMPM_OK;
+  hipLaunchKernelGGL(k_set_poses, dim3((work + 255) / 256), dim3(256), 0, st, h->poses_dev,
+                     (const float*)h->times_dev, (const RotRec*)h->rot_dev, n, h->n_rot);
+  GSMPM_LAUNCH_CHECK();
+  return GSMPM_OK;
+}
 static int upload_times(gsmpm_mpm* h, const double* time, int n, hipStream_t st) {
+  const bool grew = n > h->times_cap;
   if (n > h->times_cap) {
     int cap = std::max(h->times_cap, 4096);
     while (cap < n) cap *= 2;
@@ -2702,6 +2836,7 @@ static int upload_times(gsmpm_mpm* h, const double* time, int n, hipStream_t st)
     hipLaunchKernelGGL(k_set_times, dim3(1), dim3(kTimeBatch), 0, st, h->times_dev + s0, m, b);
     GSMPM_LAUNCH_CHECK();
   }
+  if (grid_rot(h)) return set_poses(h, n, grew, st);
   return GSMPM_OK;
 }
 
@@ -3251,8 +3386,10 @@ int gsmpm_mpm_add_plane_collider(gsmpm_mpm* h, const double p[3], const double n
 // arguments of solver.py:140-147).  Refused, with nothing changed, where no
 // EXT grid update exists: a slab's grid pass (slab.h) and the folded staging
 // of k_fused (GSMPM_FOLD=1) apply the plain node_update.
-// mv: the record's motion (gsmpm_mpm_add_moving_collider), nullptr for a static one
-static int add_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_collider_motion* mv) {
+// mv: the record's motion (gsmpm_mpm_add_moving_collider), nullptr for a static one;
+// sp: its spin as well (gsmpm_mpm_add_rotating_collider, with mv the spin's velocity and window)
+static int add_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_collider_motion* mv,
+                        const gsmpm_collider_spin* sp = nullptr) {
   if (h->slab) {
     set_error("gsmpm_mpm_add_collider: extended colliders are not supported on a slab of a multi-GPU domain "
               "(its grid passes apply fixed cubes and plane colliders only)");
@@ -3294,10 +3431,30 @@ static int add_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_colli
   h->host_bc.ext[o] = GridOpExt{c->shape, c->surface, (float)c->damping};
   ++h->n_ext;
   h->host_bc.mov[o] = GridOpMov{};
+  h->host_bc.rot[o] = GridOpRot{-1, {0.f, 0.f, 0.f}};
   if (mv) {
     h->host_bc.mov[o] = GridOpMov{{(float)mv->velocity[0], (float)mv->velocity[1], (float)mv->velocity[2]},
                                   (float)mv->t_start, (float)mv->t_end, 1};
     ++h->n_mov;
+    if (sp) {  // the pose launch of upload_times below reads the record from the device
+      const GridOpMov& m = h->host_bc.mov[o];
+      const double wm = std::sqrt(sp->omega[0] * sp->omega[0] + sp->omega[1] * sp->omega[1] + sp->omega[2] * sp->omega[2]);
+      RotRec& r = h->host_rot[h->n_rot];
+      r = RotRec{};
+      r.wm = wm;
+      r.t0 = m.t0;
+      r.t1 = m.t1;
+      for (int d = 0; d < 3; ++d) {
+        r.k[d] = sp->omega[d] / wm;
+        r.w[d] = m.w[d];
+        r.piv[d] = (float)sp->pivot[d];
+        r.a[d] = op.a[d];
+      }
+      h->host_bc.rot[o] = GridOpRot{h->n_rot, {(float)sp->omega[0], (float)sp->omega[1], (float)sp->omega[2]}};
+      if (!h->rot_dev) GSMPM_HIP(alloc(h, &h->rot_dev, (size_t)kMaxBC, kMemCommon, kFillZero));
+      GSMPM_HIP(hipMemcpy(h->rot_dev, h->host_rot, sizeof(h->host_rot), hipMemcpyHostToDevice));
+      ++h->n_rot;
+    }
     const int rt = upload_times(h, nullptr, 1, nullptr);  // the table exists, and reads t = 0 until a timed step
     if (rt) return rt;
   }
@@ -3320,6 +3477,46 @@ int gsmpm_mpm_add_moving_collider(gsmpm_mpm* h, const gsmpm_collider* c, const g
   GSMPM_REQUIRE(!std::isnan(mv->t_end), "gsmpm_mpm_add_moving_collider: t_end is NaN");
   GSMPM_REQUIRE(mv->t_end >= mv->t_start, "gsmpm_mpm_add_moving_collider: t_end < t_start");
   return add_collider(h, c, mv);
+}
+
+// A rotating record: the moving record plus an angular velocity about a pivot
+// that travels with it.  Refused wherever gsmpm_mpm_add_moving_collider is,
+// in its words; a zero omega is refused too, the two forms not being bit-equal.
+int gsmpm_mpm_add_rotating_collider(gsmpm_mpm* h, const gsmpm_collider* c, const gsmpm_collider_spin* sp) {
+  GSMPM_REQUIRE(h && c && sp, "gsmpm_mpm_add_rotating_collider: null argument");
+  GSMPM_REQUIRE(std::isfinite(sp->omega[0]) && std::isfinite(sp->omega[1]) && std::isfinite(sp->omega[2]),
+                "gsmpm_mpm_add_rotating_collider: non-finite omega");
+  GSMPM_REQUIRE(std::isfinite(sp->pivot[0]) && std::isfinite(sp->pivot[1]) && std::isfinite(sp->pivot[2]),
+                "gsmpm_mpm_add_rotating_collider: non-finite pivot");
+  GSMPM_REQUIRE(sp->omega[0] != 0 || sp->omega[1] != 0 || sp->omega[2] != 0,
+                "gsmpm_mpm_add_rotating_collider: omega is zero; add a record that does not turn with "
+                "gsmpm_mpm_add_moving_collider");
+  gsmpm_collider_motion mv;
+  for (int d = 0; d < 3; ++d) mv.velocity[d] = sp->velocity[d];
+  mv.t_start = sp->t_start;
+  mv.t_end = sp->t_end;
+  GSMPM_REQUIRE(std::isfinite(mv.velocity[0]) && std::isfinite(mv.velocity[1]) && std::isfinite(mv.velocity[2]),
+                "gsmpm_mpm_add_moving_collider: non-finite velocity");
+  GSMPM_REQUIRE(std::isfinite(mv.t_start), "gsmpm_mpm_add_moving_collider: non-finite t_start");
+  GSMPM_REQUIRE(!std::isnan(mv.t_end), "gsmpm_mpm_add_moving_collider: t_end is NaN");
+  GSMPM_REQUIRE(mv.t_end >= mv.t_start, "gsmpm_mpm_add_moving_collider: t_end < t_start");
+  return add_collider(h, c, &mv, sp);
+}
+
+// The poses of the last step call's first n_substeps substeps (diagnostics).
+int gsmpm_mpm_get_poses(gsmpm_mpm* h, int32_t n_substeps, float* out, void* stream) {
+  GSMPM_REQUIRE(h && out, "gsmpm_mpm_get_poses: null argument");
+  if (!grid_rot(h)) {
+    set_error("gsmpm_mpm_get_poses: the handle holds no rotating collider");
+    return GSMPM_ESTATE;
+  }
+  GSMPM_REQUIRE(n_substeps >= 0 && n_substeps <= h->poses_n,
+                "gsmpm_mpm_get_poses: more substeps than the last step call had");
+  GSMPM_HIP(hipStreamSynchronize((hipStream_t)stream));
+  if (n_substeps > 0)
+    GSMPM_HIP(hipMemcpy(out, h->poses_dev, sizeof(float) * kPoseFloats * (size_t)n_substeps * h->n_rot,
+                        hipMemcpyDeviceToHost));
+  return GSMPM_OK;
 }
 
 namespace gsmpm {

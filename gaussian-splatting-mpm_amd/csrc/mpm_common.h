@@ -73,13 +73,32 @@ struct GridOpMov {
   float w[3], t0, t1;
   int moving;
 };
+// The spin of a rotating record (gsmpm_mpm_add_rotating_collider): idx is the
+// record's index among the table's rotating records -- its column of the pose
+// table -- or -1 for any other op; om the angular velocity, f32 of the caller's
+// doubles.  Its mov[] entry holds w, t0 and t1.  The rest of the spin (axis,
+// |omega|, pivot) stays with k_set_poses (RotRec).
+struct GridOpRot {
+  int idx;
+  float om[3];
+};
 struct BcTable {
   int n_imp, n_ops;
   Impulse imp[kMaxBC];
   GridOp op[kMaxBC];
   GridOpExt ext[kMaxBC];  // parallel to op[], after it: the offsets the plain instantiations read do not move
   GridOpMov mov[kMaxBC];  // parallel again, after ext[]: read by the MOV instantiations only
+  GridOpRot rot[kMaxBC];  // parallel again, after mov[]: read by the ROT instantiations only
 };
+// One rotating record as k_set_poses reads it: unit axis k and |omega| in f64
+// (the angle is wm * tau in f64), the rest f32 of the caller's doubles.
+struct RotRec {
+  double k[3], wm;
+  float w[3], piv[3], a[3], t0, t1;
+  int pad;
+};
+// One pose of the pose table: {R[9] row-major, c[3], o[3], pad}
+constexpr int kPoseFloats = 16;
 
 #ifndef GSMPM_PSTORE
 #define GSMPM_PSTORE 2

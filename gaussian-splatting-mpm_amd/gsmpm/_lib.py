@@ -53,6 +53,12 @@ class ColliderMotion(ctypes.Structure):
     _fields_ = [("velocity", ctypes.c_double * 3), ("t_start", ctypes.c_double), ("t_end", ctypes.c_double)]
 
 
+class ColliderSpin(ctypes.Structure):
+    """gsmpm_collider_spin (include/gsmpm.h)."""
+    _fields_ = [("velocity", ctypes.c_double * 3), ("t_start", ctypes.c_double), ("t_end", ctypes.c_double),
+                ("omega", ctypes.c_double * 3), ("pivot", ctypes.c_double * 3)]
+
+
 class RasterArgs(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32), ("D", ctypes.c_int32), ("M", ctypes.c_int32),
@@ -100,6 +106,9 @@ _SIGS = {
     "gsmpm_mpm_step_timed": (ctypes.c_int, [c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32),
                                             ctypes.POINTER(ctypes.c_double), c_void_p]),
     "gsmpm_mpm_graph_count": (ctypes.c_int, [c_void_p]),
+    "gsmpm_mpm_add_rotating_collider": (ctypes.c_int, [c_void_p, ctypes.POINTER(Collider),
+                                                       ctypes.POINTER(ColliderSpin)]),
+    "gsmpm_mpm_get_poses": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), c_void_p]),
     "gsmpm_rccl_unique_id": (ctypes.c_int, [c_void_p]),
     "gsmpm_rccl_comm_init": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void_p)]),
     "gsmpm_rccl_comm_destroy": (ctypes.c_int, [c_void_p]),

@@ -87,7 +87,8 @@ class Simulator:
                      "add_plane_collider")
 
     def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, *, point=None, normal=None,
-                     center=None, radius=None, half=None, velocity=None, move_start=None, move_end=None) -> int:
+                     center=None, radius=None, half=None, velocity=None, move_start=None, move_end=None,
+                     angular_velocity=None, pivot=None) -> int:
         """An extended collider (gsmpm_mpm_add_collider; no reference counterpart):
         ``shape`` "plane" (point, normal), "ball" (center, radius), "box" or
         "walls" (center, half: a solid box / everything outside it), ``surface``
@@ -99,7 +100,14 @@ class Simulator:
         while move_start <= time < move_end (defaults 0 and +inf) on the
         clock the caller hands ``step`` as ``times``, stands at its placement
         before and where it arrived after, and acts on the velocity relative
-        to its own."""
+        to its own.
+
+        ``angular_velocity`` (a vector, radians per unit of that clock) makes
+        it a rotating record (gsmpm_mpm_add_rotating_collider): inside the
+        same window it also turns about ``pivot``, a point of the axis that
+        travels with the body (default: the record's point or centre, so the
+        body spins in place); ``velocity`` may be combined with it and
+        defaults to zero.  None or all zeros routes to the entries above."""
         if shape not in _lib.SHAPE:
             raise ValueError(f"add_collider: unknown shape {shape!r} (one of {sorted(_lib.SHAPE)})")
         if surface not in _lib.SURFACE:
@@ -116,6 +124,20 @@ class Simulator:
         c.a[:] = [float(a) for a in given[want[0]]]
         c.b[:] = [float(radius), 0.0, 0.0] if shape == "ball" else [float(a) for a in given[want[1]]]
         c.friction, c.damping = float(friction), float(damping)
+        spins = angular_velocity is not None and any(float(a) != 0.0 for a in angular_velocity)
+        if pivot is not None and angular_velocity is None:
+            raise TypeError("add_collider: a pivot needs an angular_velocity")
+        if spins:
+            sp = _lib.ColliderSpin()
+            sp.velocity[:] = [0.0, 0.0, 0.0] if velocity is None else [float(a) for a in velocity]
+            sp.t_start = 0.0 if move_start is None else float(move_start)
+            sp.t_end = float("inf") if move_end is None else float(move_end)
+            sp.omega[:] = [float(a) for a in angular_velocity]
+            sp.pivot[:] = list(c.a) if pivot is None else [float(a) for a in pivot]
+            bit = check(LIB.gsmpm_mpm_add_rotating_collider(self._h, ctypes.byref(c), ctypes.byref(sp)),
+                        "add_collider")
+            self._n_rot = getattr(self, "_n_rot", 0) + 1  # the width of poses()
+            return bit
         if velocity is None:
             if move_start is not None or move_end is not None:
                 raise TypeError("add_collider: move_start / move_end need a velocity")
@@ -125,6 +147,16 @@ class Simulator:
         m.t_start = 0.0 if move_start is None else float(move_start)
         m.t_end = float("inf") if move_end is None else float(move_end)
         return check(LIB.gsmpm_mpm_add_moving_collider(self._h, ctypes.byref(c), ctypes.byref(m)), "add_collider")
+
+    def poses(self, n: int):
+        """The poses of the rotating colliders on the first n substeps of the
+        last step call, a float32 array [n, rotating records, 16]: R (9, row
+        major), c, o, 0 (gsmpm_mpm_get_poses; diagnostics, waits for the stream)."""
+        import numpy as np
+        n, n_rot = int(n), getattr(self, "_n_rot", 0)
+        buf = (ctypes.c_float * max(16 * n_rot * n, 1))()
+        check(LIB.gsmpm_mpm_get_poses(self._h, n, buf, stream_of(self.device)), "gsmpm_mpm_get_poses")
+        return np.frombuffer(buf, dtype=np.float32, count=16 * n_rot * n).reshape(n, n_rot, 16).copy()
 
     def graph_count(self) -> int:
         """Step graphs the handle caches now (gsmpm_mpm_graph_count; diagnostics)."""

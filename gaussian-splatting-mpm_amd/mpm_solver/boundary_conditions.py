@@ -141,7 +141,11 @@ class ColliderBC:
     grid kernels (gsmpm_mpm_add_collider).  isCollide stays False: unlike the
     legacy plane collider this one honours its window.  With a ``velocity``
     it is a moving record (gsmpm_mpm_add_moving_collider): it translates while
-    move_start <= time < move_end (defaults: start_time, end_time)."""
+    move_start <= time < move_end (defaults: start_time, end_time).  With an
+    ``angular_velocity`` it is a rotating record
+    (gsmpm_mpm_add_rotating_collider): in the same window it also turns about
+    ``pivot`` (default: its point or centre); ``velocity`` then defaults to
+    zero."""
 
     _geometry = {"plane": ("point", "normal"), "ball": ("center", "radius"), "box": ("center", "half"),
                  "walls": ("center", "half")}
@@ -161,15 +165,26 @@ class ColliderBC:
         self.geometry = {k: bc_args[k] for k in self._geometry[self.shape]}  # KeyError names the missing one
         # a moving record: velocity, and the window of the motion (default: the activity window)
         self.velocity = bc_args.get("velocity")
+        # a rotating record: angular velocity and pivot (default: the point or centre), in the same window
+        self.angular_velocity = bc_args.get("angular_velocity")
+        self.pivot = bc_args.get("pivot")
+        if self.pivot is not None and self.angular_velocity is None:
+            raise TypeError("collider: a pivot needs an angular_velocity")
+        spins = self.angular_velocity is not None and any(float(a) != 0.0 for a in self.angular_velocity)
         self.motion = {}
-        if self.velocity is not None:
+        if self.velocity is not None or spins:
             ms, me = bc_args.get("move_start"), bc_args.get("move_end")
             self.move_start = self.start_time if ms is None else float(ms)
             self.move_end = self.end_time if me is None else float(me)
-            self.motion = dict(velocity=[float(a) for a in self.velocity], move_start=self.move_start,
-                               move_end=self.move_end)
+            self.motion = dict(move_start=self.move_start, move_end=self.move_end)
+            if self.velocity is not None:
+                self.motion["velocity"] = [float(a) for a in self.velocity]
+            if spins:
+                self.motion["angular_velocity"] = [float(a) for a in self.angular_velocity]
+                if self.pivot is not None:
+                    self.motion["pivot"] = [float(a) for a in self.pivot]
         elif bc_args.get("move_start") is not None or bc_args.get("move_end") is not None:
-            raise TypeError("collider: move_start / move_end need a velocity")
+            raise TypeError("collider: move_start / move_end need a velocity or an angular_velocity")
         self.isCollide = False
         self.bit = None  # library bc id (bit of the activity mask)
 

@@ -167,7 +167,7 @@ class MPM_Simulator:
         self.grid_postprocess.append(cl)
 
     def add_collider(self, shape, surface="separate", friction=0.0, damping=1.0, start_time=0.0, end_time=999.0,
-                     velocity=None, move_start=None, move_end=None, **geometry):
+                     velocity=None, move_start=None, move_end=None, angular_velocity=None, pivot=None, **geometry):
         """An extended collider (not in the reference; add_surface_collider above
         stays the legacy plane): ``shape`` "plane" (point=, normal=), "ball"
         (center=, radius=), "box" or "walls" (center=, half=); ``surface``
@@ -176,14 +176,16 @@ class MPM_Simulator:
         the library's bc id).  Same record as a ``{"type": "collider", ...}``
         entry of set_boundary_conditions.  ``velocity`` makes it a moving
         record: it translates while move_start <= time < move_end (defaults:
-        start_time, end_time) on the same clock, whether active or not."""
+        start_time, end_time) on the same clock, whether active or not.
+        ``angular_velocity`` makes it a rotating record: in the same window it
+        also turns about ``pivot`` (default: its point or centre)."""
         if self.fitting:
             raise TypeError("add_collider applies to the forward-only simulator; the fitting path (MPM_state_opt) "
                             "has no extended colliders")
         bc = ColliderBC(self.n_particles, dict(geometry, type="collider", shape=shape, surface=surface,
                                                friction=friction, damping=damping, start_time=start_time,
                                                end_time=end_time, velocity=velocity, move_start=move_start,
-                                               move_end=move_end))
+                                               move_end=move_end, angular_velocity=angular_velocity, pivot=pivot))
         self._add_collider_bc(bc)
         return bc
 

@@ -192,6 +192,67 @@ int gsmpm_mpm_step_timed(gsmpm_mpm* h, float dt, int32_t n_substeps, const uint3
                          void* stream);
 /* The step graphs the handle caches now (diagnostics). */
 int gsmpm_mpm_graph_count(gsmpm_mpm* h);
+
+/* Rotating colliders: a moving record (above, unchanged) that also turns with
+ * a constant angular velocity about a pivot which travels with the body.  No
+ * reference counterpart; the semantics are this library's (DESIGN.md
+ * "Rotating colliders").
+ * Stored at add time: w32, om32 = f32(omega), t0, t1 and piv32, each the f32
+ * of the double given; wm = |omega| and the unit axis k = omega / wm, computed
+ * and kept in f64 for the pose.
+ * Pose on a substep whose time reads t (f32 of the double); tc, tau and the
+ * moving flag are the moving record's:
+ *   tc = fminf(fmaxf(t, t0), t1)     tau = tc - t0     mov = t >= t0 && t < t1
+ *   theta = wm * (double)tau                                   (f64)
+ *   R = I + sin(theta) K + (1 - cos(theta)) K K                (f64; K the
+ *       cross-product matrix of k, K K its matrix square), each of the nine
+ *       entries then rounded to f32
+ *   o = piv32 + w32 * tau            (f32, unfused, per component)
+ *   c = o + R (a - piv32)            (f32, unfused, row sums left to right;
+ *       a is the record's point or centre)
+ * Action on a massive node at p, all f32, unfused, left to right, row and
+ * column sums in index order 0, 1, 2:
+ *   q = p - c          d = R^T q     (the node in the body frame)
+ *   r = p - o          wc = mov ? w32 + om32 x r : 0
+ *       ((om32 x r)[0] = om32[1] r[2] - om32[2] r[1], and cyclically)
+ *   u = R^T (v - wc)                 (the relative velocity in the body frame)
+ *   the extended record acts on u with the node offset d in place of p - a
+ *   and its own b (plane normal, radius, half extents): inside test, normal
+ *   choice, response, friction and damping are gsmpm_mpm_add_collider's,
+ *   with the box tie rule, the per-violated-axis loop of WALLS, the sticky
+ *   centre of a ball and the damping applied once;
+ *   where the record hit the node v = R u + wc, otherwise v keeps its bits.
+ * Outside the window the record stands (wc = 0) in the pose of t0 before it
+ * and in the pose of t1 from its end on.  The activity bit means what it does
+ * for a moving record: the clock runs while the record is switched off.
+ * Returns the bc id, or GSMPM_EINVAL: everything gsmpm_mpm_add_moving_collider
+ * refuses, a non-finite omega or pivot, and an all-zero omega (use
+ * gsmpm_mpm_add_moving_collider: the two are not bit-equal, and a silent
+ * fallback would hide that).  GSMPM_ESTATE as gsmpm_mpm_add_moving_collider:
+ * a slab handle (and gsmpm_mpm_slab_init refuses a handle that holds such a
+ * record), a handle created with GSMPM_FOLD=1; gsmpm_mpm_step refuses a handle
+ * that holds one; gsmpm_mpm_time_kernels and gsmpm_mpm_profile_substeps run it
+ * at t = 0.  The differentiable simulator (gsmpm_fit_*) has no colliders of
+ * this kind.  The first rotating record switches the handle to the ROT
+ * instantiations of the grid kernels, which read one 16-float pose
+ * {R[9], c[3], o[3], 0} per substep and rotating record from a table that
+ * gsmpm_mpm_step_timed fills on `stream` right after the times (sin and cos
+ * are evaluated there, once per substep and record, never in the grid
+ * kernel); a translating or static record in such a table gives what the MOV
+ * / EXT instantiations give. */
+typedef struct {
+  double velocity[3];     /* w, as gsmpm_collider_motion (may be all zero) */
+  double t_start, t_end;  /* motion window [t_start, t_end) on the caller's clock */
+  double omega[3];        /* angular velocity vector, radians per unit of that clock */
+  double pivot[3];        /* a point of the axis at t_start, grid space */
+} gsmpm_collider_spin;
+int gsmpm_mpm_add_rotating_collider(gsmpm_mpm* h, const gsmpm_collider* collider,
+                                    const gsmpm_collider_spin* spin);
+/* Diagnostics: synchronizes `stream` and copies the poses of the last step
+ * call, out[n_substeps][n_rot][16], rotating records in table order.
+ * GSMPM_ESTATE on a handle without rotating records, GSMPM_EINVAL for more
+ * substeps than that call had. */
+int gsmpm_mpm_get_poses(gsmpm_mpm* h, int32_t n_substeps, float* out /* [n_substeps][n_rot][16] */, void* stream);
 /* Synchronizes `stream`, then GSMPM_ESTATE if any substep so far produced a
  * non-finite particle state (position, mass, velocity, C or stress; clear
  * != 0 resets the word; set_particles does too), else GSMPM_OK.  No
