@@ -7,7 +7,9 @@ JSON; JSON keys a group does not declare are ignored (which is why lego.json's
 underscore adds a one-letter short flag.  Additions (all default-off):
 MPMParams.jelly_fcr (fix SURVEY F3), ModelParams.synthetic (generate
 Gaussians when the scene's PLY is absent / an LFS pointer),
-RenderParams.rotate_sh (SH view directions follow particle_R).
+RenderParams.rotate_sh (SH view directions follow particle_R),
+and the optional top-level ``particle_filling`` record (FillingParams: JSON
+only, no flags; absent = no filling).
 """
 from argparse import ArgumentParser
 
@@ -86,3 +88,23 @@ class RenderParams(ParamGroup):
         self.save_pcd_interval = 10
         self.rotate_sh = False  # shade each Gaussian at particle_R d (PhysGaussian's f_0(R^T d))
         super().__init__(parser, "Render Parameters", json_params)
+
+
+class FillingParams:
+    """The config's optional ``particle_filling`` record (interior filling of the
+    simulatable Gaussians before the simulation; DESIGN.md "Interior filling").
+    Not a flag group: the record is either absent (extract() is None and
+    nothing is filled) or a dict of these keys over their defaults."""
+    DEFAULTS = {"n_grid": 128, "density_threshold": 0.5, "support": 4, "min_hits": 6, "parity_dir": -1,
+                "per_cell": 1, "seed": 0, "max_particles": None, "boundary": None}
+
+    def __init__(self, json_params=None):
+        self.record = None
+        if json_params is not None:
+            unknown = set(json_params) - set(self.DEFAULTS)
+            if unknown:
+                raise ValueError(f"particle_filling: unknown keys {sorted(unknown)}")
+            self.record = {**self.DEFAULTS, **json_params}
+
+    def extract(self):
+        return None if self.record is None else dict(self.record)

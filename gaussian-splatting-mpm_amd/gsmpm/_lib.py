@@ -86,6 +86,24 @@ class FitParams(ctypes.Structure):
     ]
 
 
+class FillParams(ctypes.Structure):
+    """gsmpm_fill_params (include/gsmpm.h)."""
+    _fields_ = [
+        ("n_grid", ctypes.c_int32),
+        ("grid_extent", ctypes.c_double),
+        ("density_threshold", ctypes.c_double),
+        ("support", ctypes.c_int32),
+        ("min_hits", ctypes.c_int32),
+        ("parity_dir", ctypes.c_int32),
+        ("per_cell", ctypes.c_int32),
+        ("seed", ctypes.c_uint32),
+        ("use_box", ctypes.c_int32),
+        ("lo", ctypes.c_float * 3),
+        ("hi", ctypes.c_float * 3),
+        ("capacity", ctypes.c_int64),
+    ]
+
+
 # entry point -> (restype, argtypes); mirrors include/gsmpm.h
 _SIGS = {
     "gsmpm_last_error": (ctypes.c_char_p, []),
@@ -163,6 +181,14 @@ _SIGS = {
                                                 ctypes.c_float, ctypes.c_int32, c_void_p, c_void_p, c_void_p]),
     "gsmpm_particle_volume": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_void_p,
                                              c_void_p, c_void_p]),
+    "gsmpm_fill_workspace_size": (ctypes.c_int, [ctypes.POINTER(FillParams), ctypes.POINTER(ctypes.c_uint64)]),
+    "gsmpm_fill_interior": (ctypes.c_int, [ctypes.POINTER(FillParams), c_void_p, c_void_p, c_void_p, ctypes.c_int64,
+                                           c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.POINTER(ctypes.c_int64), c_void_p]),
+    "gsmpm_fill_emit": (ctypes.c_int, [ctypes.POINTER(FillParams), c_void_p, ctypes.c_uint64, c_void_p, c_void_p]),
+    "gsmpm_fill_nearest": (ctypes.c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
+    "gsmpm_fill_get_grid": (ctypes.c_int, [ctypes.POINTER(FillParams), c_void_p, ctypes.c_uint64, ctypes.c_int32,
+                                           c_void_p, c_void_p]),
     "gsmpm_fit_create": (ctypes.c_int, [ctypes.POINTER(FitParams), ctypes.POINTER(c_void_p)]),
     "gsmpm_fit_destroy": (ctypes.c_int, [c_void_p]),
     "gsmpm_fit_set_particles": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -3,6 +3,11 @@
     python main.py --config_path configs/lego.json [--n_grid 128] [--synthetic 100000]
                    [--output_path out/lego] [--white_background] [--save_pcd]
 
+A config may carry an optional top-level ``particle_filling`` record (not in
+the reference's main.py; PhysGaussian's internal filling): the simulatable
+Gaussians are then filled in grid space and the solver and the renderer see
+sources + filled particles.  Without it nothing changes.
+
 Same pipeline as main.py:164-335 of the reference: load Gaussians, sim-area
 mask (inclusive bounds), world2grid, orbit camera (az 130, el 10, r 5.75, F16),
 particle volumes, MPM_Simulator with the config's BCs plus the ground collider
@@ -29,12 +34,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from arguments import ModelParams, MPMParams, RenderParams  # noqa: E402
+from arguments import FillingParams, ModelParams, MPMParams, RenderParams  # noqa: E402
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer  # noqa: E402
 from gaussian_splatting.scene import GaussianModel  # noqa: E402
 from gaussian_splatting.utils.graphics_utils import focal2fov, getProjectionMatrix, getWorld2View2  # noqa: E402
 from gaussian_splatting.utils.system_utils import searchForMaxIteration  # noqa: E402
-from internel_filling.filling import get_particle_volume  # noqa: E402
+from internel_filling.filling import fill_particles, get_particle_volume, init_filled_particles  # noqa: E402
 from mpm_solver.solver import MPM_Simulator  # noqa: E402
 from utils.render_utils import TinyCam, to8b  # noqa: E402
 from utils.transform_utils import (apply_cov_rotations, apply_inverse_cov_rotations, apply_inverse_rotations,  # noqa: E402
@@ -105,10 +110,12 @@ def modify_cam(cam: TinyCam, center_view_world_space, observant_coordinates, dev
 
 
 def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, bg_color, args, rotation_matrices,
-                 pos_center, scaling_modifier=1.0, to_host=True, sh_rotations=None):
+                 pos_center, scaling_modifier=1.0, to_host=True, sh_rotations=None, shs=None, opacities=None):
     """main.py:108-157 (render-space transform with scaling_modifier = 1.0).
     sh_rotations (--rotate_sh; not in the reference): the per-Gaussian view-direction
-    rotations for the render-space means, MPM_Simulator.sh_rotations(A)."""
+    rotations for the render-space means, MPM_Simulator.sh_rotations(A).
+    shs / opacities: per-particle values when the particles are not pc's masked
+    Gaussians alone (interior filling appends particles)."""
     settings = GaussianRasterizationSettings(
         image_height=cam.height, image_width=cam.width, tanfovx=math.tan(cam.FovX * 0.5),
         tanfovy=math.tan(cam.FovY * 0.5), bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=cam.view_mat,
@@ -118,9 +125,9 @@ def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, b
     means3D = apply_inverse_rotations(undotransform2origin(undoshift2center111(sim_means3D), scaling_modifier,
                                                            pos_center), rotation_matrices)
     covs = apply_inverse_cov_rotations(sim_covs / (scaling_modifier * scaling_modifier), rotation_matrices)
-    image, _ = rasterizer(means3D=means3D, means2D=None, shs=pc.get_features[mask], colors_precomp=None,
-                          opacities=pc.get_opacity[mask], scales=None, rotations=None, cov3D_precomp=covs,
-                          sh_rotations=sh_rotations)
+    image, _ = rasterizer(means3D=means3D, means2D=None, shs=pc.get_features[mask] if shs is None else shs,
+                          colors_precomp=None, opacities=pc.get_opacity[mask] if opacities is None else opacities,
+                          scales=None, rotations=None, cov3D_precomp=covs, sh_rotations=sh_rotations)
     return image.detach().cpu().numpy().transpose(1, 2, 0) if to_host else image
 
 
@@ -174,7 +181,7 @@ class FrameWriter:
         self.pool.shutdown()
 
 
-def simulate(model_args, sim_args, render_args):
+def simulate(model_args, sim_args, render_args, fill_args=None):
     dev = torch.device("cuda")
     gaussians = load_model(model_args)
     cams = load_cameras(model_args)
@@ -199,6 +206,19 @@ def simulate(model_args, sim_args, render_args):
         pos_center)
     cam = modify_cam(cams[0], center_w, obs, device=dev)
     cam.toCuda(dev)
+    n_src = xg.shape[0]
+    fill_shs = fill_opa = None  # per-particle SH / opacity of sources + filled; None = the Gaussians' own
+    if fill_args is not None:
+        # interior filling in grid space; the filled particles copy their nearest source Gaussian
+        new_x = fill_particles(xg, covs_g, gaussians.get_opacity[mask].detach(),
+                               dict(fill_args, grid_extent=sim_args.grid_extent))
+        print(f"Number of filled particles: {new_x.shape[0]}")
+        fill_shs, fill_opa, covs_g = init_filled_particles(xg, gaussians.get_features[mask].detach(), covs_g,
+                                                            gaussians.get_opacity[mask].detach(), new_x)
+        xg = torch.cat([xg, new_x], dim=0)
+        half = torch.ones(3, device=dev) * sim_args.grid_extent / 2.0
+        sim_means3D = torch.cat([sim_means3D, (new_x - half) / s + pos_center], dim=0)  # world2grid undone
+        sim_covs = covs_g / (s * s)
     vols = get_particle_volume(xg, sim_args)
     solver = MPM_Simulator(xg, covs_g, vols, sim_args)
     solver.set_boundary_conditions(sim_args.boundary_conditions, sim_args)
@@ -212,7 +232,7 @@ def simulate(model_args, sim_args, render_args):
     writer = FrameWriter(out_images, seq)
     # frame 0 precedes every postprocess: no rotation yet
     writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot, pos_center,
-                               to_host=False), 0)
+                               to_host=False, shs=fill_shs, opacities=fill_opa), 0)
     t0 = time.time()
     for fid in range(1, render_args.num_frames + 1):
         for _ in range(sim_args.steps_per_frame):
@@ -224,11 +244,12 @@ def simulate(model_args, sim_args, render_args):
             g2._set(*[t.detach().cpu().numpy() for t in (gaussians._xyz, gaussians._features_dc,
                                                           gaussians._features_rest, gaussians._opacity,
                                                           gaussians._scaling, gaussians._rotation)])
-            g2._xyz[mask] = sim_means3D
+            g2._xyz[mask] = sim_means3D[:n_src]  # the original Gaussians only, not the filled particles
             g2.save_ply(os.path.join(render_args.output_path, "point_cloud", f"iteration_{fid}", "point_cloud.ply"))
         sh_rot = solver.sh_rotations(sh_A) if rotate_sh else None
         writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot,
-                                   pos_center, to_host=False, sh_rotations=sh_rot), fid)
+                                   pos_center, to_host=False, sh_rotations=sh_rot, shs=fill_shs,
+                                   opacities=fill_opa), fid)
         if fid % 10 == 0 or fid == render_args.num_frames:
             el = time.time() - t0
             print(f"frame {fid}/{render_args.num_frames}  {fid / el:.1f} fps (sim+render+png)", flush=True)
@@ -255,8 +276,9 @@ def main(argv=None):
     m = ModelParams(parser, config["model"])
     s = MPMParams(parser, config["mpm"])
     r = RenderParams(parser, config["render"])
+    fill = FillingParams(config.get("particle_filling"))
     args = parser.parse_args(rest)
-    simulate(m.extract(args), s.extract(args), r.extract(args))
+    simulate(m.extract(args), s.extract(args), r.extract(args), fill.extract())
 
 
 if __name__ == "__main__":

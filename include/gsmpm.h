@@ -565,6 +565,53 @@ int gsmpm_constitutive_mixed(const float* material, const float* F_trial, int32_
 int gsmpm_particle_volume(const float* x, int32_t n, int32_t n_grid, double grid_extent, int32_t* scratch,
                           float* vol_out, void* stream);
 
+/* ------------------------------------------------- interior filling ---
+ * The first half of PhysGaussian's internal-filling pass (fill_particles,
+ * internel_filling/filling.py): new particles inside a hollow shell of
+ * Gaussians.  No handle: the caller owns one workspace of
+ * gsmpm_fill_workspace_size bytes (256-byte aligned) that carries the grids
+ * from gsmpm_fill_interior to gsmpm_fill_emit / gsmpm_fill_get_grid, which
+ * take the same params.  Semantics, the fixed-point quantum and the hash are
+ * in DESIGN.md "Interior filling".  The fill grid is its own: n_grid here is
+ * independent of the simulation's.  Linear cell = (i * n + j) * n + l for
+ * cell (i, j, l) = floor(x / dx) per axis. */
+typedef struct {
+  int32_t n_grid;             /* 4..512 */
+  double grid_extent;         /* > 0 */
+  double density_threshold;   /* > 0; occupied = density > threshold */
+  int32_t support;            /* 0..16: largest stamp half-width in cells */
+  int32_t min_hits;           /* 1..6 of the six axis directions must meet an occupied cell */
+  int32_t parity_dir;         /* -1 off; 0..5 = +x -x +y -y +z -z: the occupied runs met that way must be odd */
+  int32_t per_cell;           /* 1..8 particles per interior cell */
+  uint32_t seed;
+  int32_t use_box;            /* != 0: only cells whose centre lies in [lo, hi] (grid space) */
+  float lo[3], hi[3];
+  int64_t capacity;           /* gsmpm_fill_emit writes at most this many particles */
+} gsmpm_fill_params;
+
+int gsmpm_fill_workspace_size(const gsmpm_fill_params* p, uint64_t* bytes);
+/* Density, occupied and interior masks and the emission offsets from x [N,3]
+ * (grid space), cov6 [N,6] (gsmpm_mpm_set_particles' layout), opacity [N].
+ * *total: particles the interior cells emit (per_cell each), whatever the
+ * capacity; *skipped: particles left out (non-finite value, opacity outside
+ * [0, 1], cell outside the grid).  Synchronises the stream once. */
+int gsmpm_fill_interior(const gsmpm_fill_params* p, const float* x, const float* cov6, const float* opacity, int64_t n,
+                        void* ws, uint64_t ws_bytes, int64_t* total, int64_t* skipped, void* stream);
+/* out_pos [min(total, capacity), 3]: the particles in linear-cell order, then
+ * k; nothing beyond is written. */
+int gsmpm_fill_emit(const gsmpm_fill_params* p, const void* ws, uint64_t ws_bytes, float* out_pos, void* stream);
+/* index[q] = the source nearest to query q (exact, f32 d2 = (dx*dx + dy*dy) +
+ * dz*dz, lowest index among equals). */
+int gsmpm_fill_nearest(const float* query, int64_t n_query, const float* source, int64_t n_source, int32_t* index,
+                       void* stream);
+#define GSMPM_FILL_DENSITY 0        /* f32 [n^3] = fixed-point sum * 2^-24 */
+#define GSMPM_FILL_OCCUPIED 1       /* u8  [n^3] */
+#define GSMPM_FILL_INTERIOR 2       /* u8  [n^3] */
+#define GSMPM_FILL_BITS 3           /* u16 [n^3]: bit d = direction d meets an occupied cell, bit 8+d = run parity */
+#define GSMPM_FILL_DENSITY_FIXED 4  /* u64 [n^3]: the fixed-point sums themselves */
+int gsmpm_fill_get_grid(const gsmpm_fill_params* p, const void* ws, uint64_t ws_bytes, int32_t which, void* out,
+                        void* stream);
+
 /* ------------------------------------------------ differentiable MPM ---
  * Replaces MPM_Simulator with args.fitting=True (solver.py:54-108,131-133,
  * 167-177) over MPM_model's logE/y/mu/lam (model.py:35-44) and
