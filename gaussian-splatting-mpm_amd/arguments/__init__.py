@@ -8,7 +8,8 @@ underscore adds a one-letter short flag.  Additions (all default-off):
 MPMParams.jelly_fcr (fix SURVEY F3), ModelParams.synthetic (generate
 Gaussians when the scene's PLY is absent / an LFS pointer),
 RenderParams.rotate_sh (SH view directions follow particle_R),
-and the optional top-level ``particle_filling`` record (FillingParams: JSON
+RenderParams.save_pcd_deformed (--save_pcd writes the deformed Gaussians as a
+standard 3DGS PLY: scales, rotations, rotated SH, filled particles), and the optional top-level ``particle_filling`` record (FillingParams: JSON
 only, no flags; absent = no filling).
 """
 from argparse import ArgumentParser
@@ -87,6 +88,7 @@ class RenderParams(ParamGroup):
         self.save_pcd = False
         self.save_pcd_interval = 10
         self.rotate_sh = False  # shade each Gaussian at particle_R d (PhysGaussian's f_0(R^T d))
+        self.save_pcd_deformed = False  # --save_pcd writes scales / rotations / SH of the deformed state too
         super().__init__(parser, "Render Parameters", json_params)
 
 

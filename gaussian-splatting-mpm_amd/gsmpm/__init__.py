@@ -5,6 +5,7 @@
 reference-shaped packages (``mpm_solver``, ``diff_gaussian_rasterization``,
 ``internel_filling``) are built on.  ``gsmpm.bc`` holds the host-side
 boundary-condition scheduling (f64 clock), ``gsmpm.dist`` the
-spatial-slab multi-GPU driver.
+spatial-slab multi-GPU driver, ``gsmpm.export`` the way back from a deformed
+state to a standard 3DGS model (scales, quaternions, rotated SH).
 """
-__all__ = ["sim", "raster", "bc", "dist"]
+__all__ = ["sim", "raster", "bc", "dist", "export"]

@@ -189,6 +189,9 @@ _SIGS = {
     "gsmpm_fill_nearest": (ctypes.c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "gsmpm_fill_get_grid": (ctypes.c_int, [ctypes.POINTER(FillParams), c_void_p, ctypes.c_uint64, ctypes.c_int32,
                                            c_void_p, c_void_p]),
+    "gsmpm_cov_to_scale_rot": (ctypes.c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsmpm_sh_rotate": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_void_p,
+                                       c_void_p]),
     "gsmpm_fit_create": (ctypes.c_int, [ctypes.POINTER(FitParams), ctypes.POINTER(c_void_p)]),
     "gsmpm_fit_destroy": (ctypes.c_int, [c_void_p]),
     "gsmpm_fit_set_particles": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,12 +1,16 @@
 """PhysGaussian simulate + render driver -- drop-in for the reference's main.py.
 
     python main.py --config_path configs/lego.json [--n_grid 128] [--synthetic 100000]
-                   [--output_path out/lego] [--white_background] [--save_pcd]
+                   [--output_path out/lego] [--white_background] [--save_pcd [--save_pcd_deformed]]
 
 A config may carry an optional top-level ``particle_filling`` record (not in
 the reference's main.py; PhysGaussian's internal filling): the simulatable
 Gaussians are then filled in grid space and the solver and the renderer see
 sources + filled particles.  Without it nothing changes.
+--save_pcd writes, as the reference does, the trained model with the moved
+means only; with --save_pcd_deformed (not in the reference) the file is the
+deformed state as any 3DGS tool reads it: scales and rotations of the deformed
+covariances, SH rotated under --rotate_sh, filled particles included.
 
 Same pipeline as main.py:164-335 of the reference: load Gaussians, sim-area
 mask (inclusive bounds), world2grid, orbit camera (az 130, el 10, r 5.75, F16),
@@ -39,6 +43,7 @@ from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianR
 from gaussian_splatting.scene import GaussianModel  # noqa: E402
 from gaussian_splatting.utils.graphics_utils import focal2fov, getProjectionMatrix, getWorld2View2  # noqa: E402
 from gaussian_splatting.utils.system_utils import searchForMaxIteration  # noqa: E402
+from gsmpm.export import deformed_model  # noqa: E402
 from internel_filling.filling import fill_particles, get_particle_volume, init_filled_particles  # noqa: E402
 from mpm_solver.solver import MPM_Simulator  # noqa: E402
 from utils.render_utils import TinyCam, to8b  # noqa: E402
@@ -240,11 +245,23 @@ def simulate(model_args, sim_args, render_args, fill_args=None):
         solver.postprocess()
         sim_means3D, sim_covs = solver._sim.world_outputs(s, pos_center.tolist(), render_space=False)
         if render_args.save_pcd and fid % render_args.save_pcd_interval == 0:
-            g2 = GaussianModel(3, device=dev)
-            g2._set(*[t.detach().cpu().numpy() for t in (gaussians._xyz, gaussians._features_dc,
-                                                          gaussians._features_rest, gaussians._opacity,
-                                                          gaussians._scaling, gaussians._rotation)])
-            g2._xyz[mask] = sim_means3D[:n_src]  # the original Gaussians only, not the filled particles
+            if getattr(render_args, "save_pcd_deformed", False):
+                # the deformed state as a standard 3DGS model: scales / rotations from the deformed
+                # covariances, SH rotated by particle_R (the Q for these world-space means) under
+                # --rotate_sh, and the filled particles as rows of their own
+                Qw = solver.sh_rotations(None) if rotate_sh else None
+                filled = None
+                if fill_shs is not None:
+                    filled = (fill_shs[n_src:], fill_opa[n_src:], sim_means3D[n_src:], sim_covs[n_src:])
+                    filled += (Qw[n_src:],) if rotate_sh else ()
+                g2 = deformed_model(gaussians, mask, sim_means3D[:n_src], sim_covs[:n_src],
+                                    sh_rotations=Qw[:n_src] if rotate_sh else None, filled=filled)
+            else:
+                g2 = GaussianModel(3, device=dev)
+                g2._set(*[t.detach().cpu().numpy() for t in (gaussians._xyz, gaussians._features_dc,
+                                                              gaussians._features_rest, gaussians._opacity,
+                                                              gaussians._scaling, gaussians._rotation)])
+                g2._xyz[mask] = sim_means3D[:n_src]  # the original Gaussians only, not the filled particles
             g2.save_ply(os.path.join(render_args.output_path, "point_cloud", f"iteration_{fid}", "point_cloud.ply"))
         sh_rot = solver.sh_rotations(sh_A) if rotate_sh else None
         writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot,

@@ -829,6 +829,43 @@ int gsmpm_raster_dsort_stats(const gsmpm_raster* r, int64_t out8[8]);
 int gsmpm_raster_mark_visible(const float* means3D, int32_t P, const float* viewmatrix, const float* projmatrix,
                               uint8_t* visible, void* stream);
 
+/* ---- export: a deformed state back to the 3DGS file format's parameters (csrc/export.hip) ----
+ * The file format holds a Gaussian as three log-scales, a quaternion and SH
+ * coefficients; the simulator ends a frame with a full covariance F Sigma F^T
+ * (gsmpm_mpm_world_outputs) and a view-direction rotation Q
+ * (gsmpm_mpm_sh_rotations).  These two device passes produce the former from
+ * the latter.  Not in the reference (its --save_pcd writes the moved means
+ * only).  Both only enqueue on `stream`.  Arguments are validated before any
+ * HIP call: n < 0, D outside 0..3, M < (D+1)^2 or, with n > 0, a null
+ * required pointer is GSMPM_EINVAL; n == 0 is GSMPM_OK with nothing launched
+ * (the arrays of an empty set may be null).
+ *
+ * gsmpm_cov_to_scale_rot: cov6 [n,6] (xx, xy, xz, yy, yz, zz) -> log_scale
+ * [n,3], quat [n,4] = (w, x, y, z), unit length, w >= 0 (the convention of
+ * GaussianModel's build_rotation), with
+ *     R(quat) diag(exp(2 log_scale)) R(quat)^T = cov
+ * from a float64 cyclic Jacobi eigen-solve (fixed sweep count).  The scales
+ * come out in descending order and R is a proper rotation (det +1), so the
+ * result is a function of the row alone.  Eigenvalues are clamped from below
+ * at max(1e-14 * lambda_max, 1e-36) before the log, so every log_scale is
+ * finite for any finite row (rank-deficient, zero, slightly indefinite from
+ * f32 rounding).  A row with a NaN or Inf entry gets the identity quaternion
+ * and the floor scale 0.5 log(1e-36) and adds one to *n_bad (device memory,
+ * may be NULL; the kernel adds, the caller zeroes).
+ *
+ * gsmpm_sh_rotate: shs [n,M,3], Q [n,3,3] row-major, degree D with
+ * M >= (D+1)^2 -> out [n,M,3] with
+ *     sh(D, out_p, d) = sh(D, shs_p, Q_p d)   for every unit d,
+ * sh the rasterizer's SH polynomial (its signs and constants), Q d the
+ * product gsmpm_raster_args.sh_rotations forms: evaluating out without
+ * sh_rotations renders what shs renders with them.  Exact (to rounding) for
+ * orthogonal Q; for a Q that is off orthogonal by delta the two sides differ
+ * by O(delta |shs|), as Y_l(Q d) then leaves band l.  Band 0 and the
+ * coefficients past (D+1)^2 are copied bit for bit.  out may be shs. */
+int gsmpm_cov_to_scale_rot(const float* cov6, int64_t n, float* log_scale, float* quat,
+                           int64_t* n_bad /* device, may be NULL */, void* stream);
+int gsmpm_sh_rotate(const float* shs, const float* Q, int64_t n, int32_t D, int32_t M, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
