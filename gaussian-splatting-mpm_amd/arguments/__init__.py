@@ -5,7 +5,12 @@ Semantics kept for the drop-in CLI: every attribute of a group becomes a
 JSON; JSON keys a group does not declare are ignored (which is why lego.json's
 ``model.white_background`` never reaches RenderParams).  A leading
 underscore adds a one-letter short flag.  Additions (all default-off):
-MPMParams.jelly_fcr (fix SURVEY F3), ModelParams.synthetic (generate
+MPMParams.jelly_fcr (fix SURVEY F3), MPMParams.yield_stress /
+plastic_viscosity / hardening / xi / friction_angle (the material constants
+model.py:48-59 hard-codes, at its values: absent = the reference's), the
+material name "fluid" (fluid_return_mapping, which the reference defines and
+never dispatches; also a modify_material name, and additional_params records
+take an optional "yield_stress": configs/lego-melt.json), ModelParams.synthetic (generate
 Gaussians when the scene's PLY is absent / an LFS pointer),
 RenderParams.rotate_sh (SH view directions follow particle_R),
 RenderParams.save_pcd_deformed (--save_pcd writes the deformed Gaussians as a
@@ -71,6 +76,12 @@ class MPMParams(ParamGroup):
         self.boundary_conditions = []
         self.fitting = False
         self.jelly_fcr = False
+        # the material constants the reference hard-codes (model.py:48-59), at its values
+        self.yield_stress = 0.005
+        self.plastic_viscosity = 0.008
+        self.hardening = 1.0
+        self.xi = 1.0
+        self.friction_angle = 25.0
         super().__init__(parser, "MPM Parameters", json_params)
 
     def extract(self, args):

@@ -45,6 +45,8 @@ namespace gsmpm {
 // F_trial, fused / phased: none 3.2e-4 / 4.6e-4, sand 3.1e-4 / 3.6e-4, foam
 // 3.2e-4 / 4.6e-4, metal 5.5e-5 / 8.9e-5, metal + foam the same, all four
 // 2.3e-5 / 4.0e-5), and the exact form costs a metal wave ~10 us a launch.
+// Bit 5 is the fluid's: clear, so a fluid row of a mixed handle runs the body
+// of the uniform fluid kernel bit for bit.
 #ifndef GSMPM_MIXED_EXACT
 #define GSMPM_MIXED_EXACT 0x2
 #endif
@@ -237,9 +239,11 @@ constexpr int kMatMixed = 6;
 // Kernel code of a stored material value, by the reference's own comparisons:
 // m == 1 metal, m == 2 sand, m == 3 foam; anything else (0, other numbers,
 // non-integers, NaN) is its `else` branch, F = F_trial with the jelly stress
-// rule of the handle (`jelly`: 0 = zero stress as written, 4 = FCR).
+// rule of the handle (`jelly`: 0 = zero stress as written, 4 = FCR).  m == 5
+// is the fluid (GSMPM_MAT_FLUID), a comparison the reference does not have:
+// the one stored value read differently from its `else`.
 __device__ __forceinline__ int material_code(float m, int jelly) {
-  return m == 1.0f ? 1 : (m == 2.0f ? 2 : (m == 3.0f ? 3 : jelly));
+  return m == 1.0f ? 1 : (m == 2.0f ? 2 : (m == 3.0f ? 3 : (m == 5.0f ? 5 : jelly)));
 }
 
 // The per-particle dispatch around the bodies above.  Every lane that
@@ -249,7 +253,8 @@ __device__ __forceinline__ int material_code(float m, int jelly) {
 // other lanes masked off.  Particles are stored in bin order, so the waves of
 // a region-painted scene almost always hold one code: they make one trip --
 // one ballot and one scalar branch on top of the uniform kernel -- and a
-// wave with k distinct codes makes k <= 4 trips.  Both kinds of wave run the
+// wave with k distinct codes makes k <= 5 trips (jelly, metal, sand, foam,
+// fluid: a handle has one jelly rule).  Both kinds of wave run the
 // same single copy of each body, so a particle's result does not depend on
 // which other particles share its wave.  Metal's body is the EXACT form.
 __device__ __forceinline__ void return_map_and_stress_mixed(int code, float (&F)[3][3], float mu, float lam, float& yld,
@@ -267,6 +272,7 @@ __device__ __forceinline__ void return_map_and_stress_mixed(int code, float (&F)
         case 2: return_map_and_stress<2, ((GSMPM_MIXED_EXACT >> 2) & 1) != 0>(F, mu, lam, yld, dt, mc, tau); break;
         case 3: return_map_and_stress<3, ((GSMPM_MIXED_EXACT >> 3) & 1) != 0>(F, mu, lam, yld, dt, mc, tau); break;
         case 4: return_map_and_stress<4, ((GSMPM_MIXED_EXACT >> 4) & 1) != 0>(F, mu, lam, yld, dt, mc, tau); break;
+        case 5: return_map_and_stress<5, ((GSMPM_MIXED_EXACT >> 5) & 1) != 0>(F, mu, lam, yld, dt, mc, tau); break;
         default: break;  // jelly as written: F kept, zero stress
       }
     }

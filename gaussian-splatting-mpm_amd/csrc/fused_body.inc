@@ -387,7 +387,7 @@
         // compute_stress_from_F_trial (utils.py:13-54)
         if constexpr (MAT == kMatMixed) {
           // the per-particle dispatch (constitutive.h).  The returned F is
-          // stored for metal / sand / foam rows (a G2P + P2G launch left
+          // stored for metal / sand / foam / fluid rows (a G2P + P2G launch left
           // F_trial to this store, so there every row: a jelly row's F is its
           // F_trial); the yield for metal rows only
           float tau[3][3];
@@ -395,7 +395,7 @@
           float yld = ps.ld(PYLD, p);
           const float mu = ps.ld(PMU, p), lam = ps.ld(PLAM, p);
           return_map_and_stress_mixed(code, F, mu, lam, yld, dt, mc, tau);
-          if (G2P || (code >= 1 && code <= 3)) {
+          if (G2P || (code >= 1 && code <= 3) || code == 5) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) ps.st(PF + i, p, F[i / 3][i % 3]);
           }
@@ -412,7 +412,7 @@
           float yld = ps.ld(PYLD, p);
           const float mu = ps.ld(PMU, p), lam = ps.ld(PLAM, p);
           return_map_and_stress<MAT>(F, mu, lam, yld, dt, mc, tau);
-          if constexpr (MAT == 1 || MAT == 2 || MAT == 3) {
+          if constexpr (MAT == 1 || MAT == 2 || MAT == 3 || MAT == 5) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) ps.st(PF + i, p, F[i / 3][i % 3]);
           }

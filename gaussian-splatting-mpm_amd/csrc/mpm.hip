@@ -177,7 +177,7 @@ __device__ __forceinline__ void particle_front(const Particles& ps, int p, const
   for (int i = 0; i < 9; ++i) nvt[i / 3][i % 3] = 0.f;
   if constexpr (MAT == kMatMixed) {
     // the per-particle dispatch (constitutive.h): F stored for metal / sand /
-    // foam rows, the yield for metal rows, nvt 0 for jelly-as-written rows
+    // foam / fluid rows, the yield for metal rows, nvt 0 for jelly-as-written rows
     float F[3][3], tau[3][3];
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i / 3][i % 3] = ps.ld(PF + i, p);
@@ -185,7 +185,7 @@ __device__ __forceinline__ void particle_front(const Particles& ps, int p, const
     float yld = ps.ld(PYLD, p);
     const float mu = ps.ld(PMU, p), lam = ps.ld(PLAM, p);
     return_map_and_stress_mixed(code, F, mu, lam, yld, dt, mc, tau);
-    if (code >= 1 && code <= 3) {
+    if ((code >= 1 && code <= 3) || code == 5) {
 #pragma unroll
       for (int i = 0; i < 9; ++i) ps.st(PF + i, p, F[i / 3][i % 3]);
     }
@@ -204,7 +204,7 @@ __device__ __forceinline__ void particle_front(const Particles& ps, int p, const
     float yld = ps.ld(PYLD, p);
     const float mu = ps.ld(PMU, p), lam = ps.ld(PLAM, p);
     return_map_and_stress<MAT>(F, mu, lam, yld, dt, mc, tau);
-    if constexpr (MAT == 1 || MAT == 2 || MAT == 3) {
+    if constexpr (MAT == 1 || MAT == 2 || MAT == 3 || MAT == 5) {
 #pragma unroll
       for (int i = 0; i < 9; ++i) ps.st(PF + i, p, F[i / 3][i % 3]);
     }
@@ -2369,6 +2369,7 @@ static int substep_begin(gsmpm_mpm* h, float dt, uint32_t mask, int c, hipStream
     case 1: launch_p2g<1>(h, c, mask, dt, st, e8); break;
     case 2: launch_p2g<2>(h, c, mask, dt, st, e8); break;
     case 3: launch_p2g<3>(h, c, mask, dt, st, e8); break;
+    case 5: launch_p2g<5>(h, c, mask, dt, st, e8); break;
     case kMatMixed: launch_p2g<kMatMixed>(h, c, mask, dt, st, e8); break;
     default: launch_p2g<4>(h, c, mask, dt, st, e8); break;
   }
@@ -2553,6 +2554,7 @@ static void launch_fused_m(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, c
     case 1: launch_fused_t<1, MODE>(h, f, st, ev); break;
     case 2: launch_fused_t<2, MODE>(h, f, st, ev); break;
     case 3: launch_fused_t<3, MODE>(h, f, st, ev); break;
+    case 5: launch_fused_t<5, MODE>(h, f, st, ev); break;
     case kMatMixed:  // mixed mode refuses the folded pipeline (enter_mixed): no FOLD instantiation of it
       if constexpr ((MODE & 4) == 0) launch_fused_t<kMatMixed, MODE>(h, f, st, ev);
       break;
@@ -3120,8 +3122,9 @@ int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
                 "gsmpm_mpm_create: n_particles too large for one domain (use slabs, < 10.7M)");
   GSMPM_REQUIRE(prm->n_grid > 0 && prm->n_grid <= 2048, "gsmpm_mpm_create: n_grid out of range");
   GSMPM_REQUIRE(prm->grid_extent > 0, "gsmpm_mpm_create: grid_extent must be > 0");
-  // model.py:27-30: anything but jelly/metal/sand/foam raises TypeError
-  if (prm->material < 0 || prm->material > 3) {
+  // model.py:27-30: anything but jelly/metal/sand/foam raises TypeError; the
+  // fluid (GSMPM_MAT_FLUID = 5) is this build's addition, 4 stays private
+  if (prm->material < 0 || (prm->material > 3 && prm->material != GSMPM_MAT_FLUID)) {
     set_error("Material not supported yet");
     return GSMPM_EINVAL;
   }
@@ -3787,7 +3790,7 @@ static RegionBox region_box(const double c[3], const double s[3]) {
 int gsmpm_mpm_set_region_material(gsmpm_mpm* h, const double center[3], const double size[3], int32_t material,
                                   void* stream) {
   GSMPM_REQUIRE(h && center && size, "gsmpm_mpm_set_region_material: null argument");
-  if (material < 0 || material > 3) {  // model.py:27-30
+  if (material < 0 || (material > 3 && material != GSMPM_MAT_FLUID)) {  // model.py:27-30, + the fluid
     set_error("Material not supported yet");
     return GSMPM_EINVAL;
   }
@@ -3961,6 +3964,7 @@ int gsmpm_mpm_time_kernels(gsmpm_mpm* h, float dt, uint32_t bc_active, int32_t r
       case 1: launch_p2g<1>(h, c, bc_active, dt, st, nullptr); break;
       case 2: launch_p2g<2>(h, c, bc_active, dt, st, nullptr); break;
       case 3: launch_p2g<3>(h, c, bc_active, dt, st, nullptr); break;
+      case 5: launch_p2g<5>(h, c, bc_active, dt, st, nullptr); break;
       case kMatMixed: launch_p2g<kMatMixed>(h, c, bc_active, dt, st, nullptr); break;
       default: launch_p2g<4>(h, c, bc_active, dt, st, nullptr); break;
     }

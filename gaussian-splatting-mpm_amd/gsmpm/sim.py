@@ -13,7 +13,9 @@ import torch
 from . import _lib
 from ._lib import LIB, check, ptr, stream_of
 
-MATERIALS = {"jelly": 0, "metal": 1, "sand": 2, "foam": 3}  # mpm_solver/utils.py:5-10
+# mpm_solver/utils.py:5-10, plus the fluid (GSMPM_MAT_FLUID: fluid_return_mapping, which the reference never dispatches)
+MATERIALS = {"jelly": 0, "metal": 1, "sand": 2, "foam": 3, "fluid": 5}
+_CODES = (0, 1, 2, 3, 5)  # 4 is private to the library (jelly + FCR: jelly_fcr=True)
 
 _WIDTH = {"x": 3, "v": 3, "C": 9, "F_trial": 9, "cov": 6, "init_cov": 6, "R": 9, "mass": 1, "vol": 1, "mu": 1,
           "lam": 1, "yield_stress": 1, "material": 1}
@@ -33,7 +35,7 @@ class Simulator:
                  keep_grid: bool = False, use_graph: bool = True, sort: bool = True, phased: bool = False,
                  device=None):
         code = MATERIALS.get(material, -1) if isinstance(material, str) else int(material)
-        if code not in (0, 1, 2, 3):
+        if code not in _CODES:
             raise TypeError("Material not supported yet")  # model.py:27-30
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.n = int(n_particles)
@@ -175,7 +177,7 @@ class Simulator:
         """modify_material (boundary_conditions.py:74-85): the particles now
         inside the box |x - center| < size get `material` (a name or a code)."""
         code = MATERIALS.get(material, -1) if isinstance(material, str) else int(material)
-        if code not in (0, 1, 2, 3):
+        if code not in _CODES:
             raise TypeError("Material not supported yet")  # model.py:27-30
         check(LIB.gsmpm_mpm_set_region_material(self._h, _d3(center), _d3(size), code, stream_of(self.device)),
               "gsmpm_mpm_set_region_material")

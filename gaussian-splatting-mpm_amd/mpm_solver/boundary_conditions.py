@@ -56,6 +56,9 @@ class MaterialParamsModifier(BasicBC):
         self.density = bc_args["density"]
         self.E = bc_args["E"]
         self.nu = bc_args["nu"]
+        # optional, not in the reference: the yield of the rows inside the box (a
+        # fluid region inside a metal body needs its own); absent: untouched
+        self.yield_stress = bc_args.get("yield_stress")
         self.isMaterial = False
         super().__init__(n_particles, bc_args, sim_args)
 
@@ -64,6 +67,10 @@ class MaterialParamsModifier(BasicBC):
         model._owner.flush()
         state._override_density(self.center, self.size, self.density)  # particle_density[p] = density (:63)
         sim.set_region_params(self.center, self.size, self.E, self.nu, self.density, self.mu)
+        if self.yield_stress is not None:
+            y = sim.get("yield_stress")
+            y[_box_mask(sim.get("x"), self.center, self.size)] = float(self.yield_stress)
+            sim.set("yield_stress", y)
 
     def applymu(self, state, model):
         """boundary_conditions.py:65-70 alone: mu inside the box, unless 1000.
@@ -75,12 +82,8 @@ class MaterialParamsModifier(BasicBC):
             return
         sim = _forward_sim(model, "additional_params")
         model._owner.flush()
-        import torch
-        x = sim.get("x")
-        c = torch.tensor(self.center, dtype=torch.float32, device=x.device)
-        sz = torch.tensor(self.size, dtype=torch.float32, device=x.device)
         mu = sim.get("mu")
-        mu[((x - c).abs() < sz).all(dim=1)] = float(self.mu)
+        mu[_box_mask(sim.get("x"), self.center, self.size)] = float(self.mu)
         sim.set("mu", mu)
 
 
@@ -106,6 +109,14 @@ class MaterialTypeModifier(BasicBC):
         sim = _forward_sim(model, "modify_material")
         model._owner.flush()
         sim.set_region_material(self.center, self.size, self.material_code)
+
+
+def _box_mask(x, center, size):
+    """The region records' box test (boundary_conditions.py:44, 60, 84): f32, strict."""
+    import torch
+    c = torch.tensor([float(v) for v in center], dtype=torch.float32, device=x.device)
+    s = torch.tensor([float(v) for v in size], dtype=torch.float32, device=x.device)
+    return ((x - c).abs() < s).all(dim=1)
 
 
 def _forward_sim(model, what):

@@ -58,16 +58,22 @@ class MPM_model:
         self.dx = args.grid_extent / args.n_grid
         self.inv_dx = args.n_grid / args.grid_extent
         code = material_types.get(args.material, -1)
-        if code not in (0, 1, 2, 3):
+        if code not in (0, 1, 2, 3, 5):
             raise TypeError("Material not supported yet")  # model.py:27-30
+        if code == 5 and bool(getattr(args, "fitting", False)):
+            # the differentiable simulator is single-material and has no fluid body
+            raise TypeError("Material not supported yet (the fluid runs on the forward-only simulator)")
         self.material_code = code
         self.gravity = list(args.gravity)
-        self.friction_angle = 25.0
+        # The reference hard-codes these five (model.py:48-59); here they are its
+        # values unless the config's mpm group carries one (MPMParams).
+        self.friction_angle = float(getattr(args, "friction_angle", 25.0))
         sin_phi = math.sin(self.friction_angle / 180.0 * 3.141592653589793)
         self.alpha = math.sqrt(2.0 / 3.0) * 2.0 * sin_phi / (3.0 - sin_phi)
-        self.hardening = 1
-        self.xi = 1
-        self.plastic_viscosity = 0.008
+        self.hardening = getattr(args, "hardening", 1)
+        self.xi = getattr(args, "xi", 1)
+        self.plastic_viscosity = getattr(args, "plastic_viscosity", 0.008)
+        self.yield_stress_init = getattr(args, "yield_stress", 0.005)  # model.py:55-56, the per-particle fill
         self.softening = 1.0
         self._logE = math.log10(args.E)
         self._y = -math.log(0.49 / args.nu - 1)

@@ -49,9 +49,12 @@ class MPM_Simulator:
             self.mpm_model._bind_fit(self)
             self.mpm_state = MPM_state_opt(self, args)
             return
+        m = self.mpm_model  # the material constants: the reference's, or the config's (MPMParams)
         self._sim = Simulator(
             self.n_particles, n_grid=args.n_grid, grid_extent=args.grid_extent, material=args.material, E=args.E,
-            nu=args.nu, density=args.density, gravity=args.gravity, jelly_fcr=bool(getattr(args, "jelly_fcr", False)),
+            nu=args.nu, density=args.density, gravity=args.gravity, yield_stress=float(m.yield_stress_init),
+            hardening=float(m.hardening), xi=float(m.xi), plastic_viscosity=float(m.plastic_viscosity),
+            friction_angle=float(m.friction_angle), jelly_fcr=bool(getattr(args, "jelly_fcr", False)),
             keep_grid=bool(getattr(args, "keep_grid", False)), phased=bool(getattr(args, "phased", False)),
             device=xyzs.device if xyzs.is_cuda else None)
         self._sim.set_particles(xyzs.reshape(-1, 3), covs.reshape(-1, 6), volumes.reshape(-1), init_v)

@@ -9,4 +9,5 @@ material_types = {
     "metal": 1,
     "sand": 2,
     "foam": 3,
+    "fluid": 5,  # fluid_return_mapping (constitutive_models.py:142-213), never dispatched by the reference; 4 is private
 }

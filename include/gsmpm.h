@@ -38,6 +38,13 @@ typedef struct gsmpm_mpm gsmpm_mpm;
 #define GSMPM_MAT_METAL 1
 #define GSMPM_MAT_SAND 2
 #define GSMPM_MAT_FOAM 3
+/* The cohesive fluid of fluid_return_mapping (constitutive_models.py:142-213,
+ * which the reference defines and never dispatches) with the StVK stress foam
+ * uses.  It lives on yield_stress (never written: the fluid does not harden)
+ * and plastic_viscosity; at the default yield 0.005 nearly all deviatoric
+ * stress is returned every substep and the bulk response is lam.  Code 4 stays
+ * private (jelly + FCR, GSMPM_FLAG_JELLY_FCR); 4, 6, 7, ... are refused. */
+#define GSMPM_MAT_FLUID 5
 
 /* flags */
 #define GSMPM_FLAG_JELLY_FCR 1u   /* fix SURVEY F3: run FCR elasticity for jelly (utils.py:37-38) */
@@ -455,10 +462,12 @@ int gsmpm_mpm_sh_rotations(gsmpm_mpm* h, const float A[9], float* out, void* str
  *     order) and enters mixed mode; no host sync, no check that they differ;
  *   - gsmpm_mpm_set_region_material enters it too.
  * In mixed mode the stress of each particle follows its own value as the
- * reference's comparisons read it: == 1 metal, == 2 sand, == 3 foam; anything
- * else (0, other numbers, NaN) is the `else` branch, F = F_trial with the
- * jelly rule of the handle (zero stress as written, SURVEY F3, or FCR when
- * created with GSMPM_FLAG_JELLY_FCR).  The re-binning interval takes the
+ * reference's comparisons read it: == 1 metal, == 2 sand, == 3 foam, and
+ * == 5 fluid (GSMPM_MAT_FLUID; the reference has no such comparison -- this
+ * is the one value whose meaning differs from its `else`); anything else (0,
+ * 4, 7, other numbers, non-integers, NaN) is the `else` branch, F = F_trial
+ * with the jelly rule of the handle (zero stress as written, SURVEY F3, or FCR
+ * when created with GSMPM_FLAG_JELLY_FCR).  The re-binning interval takes the
  * stress-bearing default unless the caller set one.  gsmpm_mpm_get works on
  * any handle; a uniform one returns the create-time code in every row.
  * On a mixed handle metal rows run the reference's own SVD sequence
@@ -468,6 +477,9 @@ int gsmpm_mpm_sh_rotations(gsmpm_mpm* h, const float A[9], float* out, void* str
  * parity bounds.  So a metal particle's results differ in the last bits
  * between a mixed and a uniform handle, and the mixed kernel costs more
  * (k_fused, lego 100k, every id metal: 33.9 us against 22.8 us a launch).
+ * Which bodies take that exact form is the build-time GSMPM_MIXED_EXACT, one
+ * bit per kernel code (default 0x2: metal; bit 5 is the fluid's, clear, so a
+ * fluid row runs the uniform fluid kernel's body bit for bit).
  * Mixed mode lasts until gsmpm_mpm_set_particles, which resets the ids to the
  * create-time material as it re-initialises mu / lam / yield.
  * Not supported (GSMPM_ESTATE, nothing launched, the message says why): a
@@ -548,14 +560,13 @@ int gsmpm_svd3(const float* A, int32_t n, float* U, float* sig, float* V, void* 
 /* Constitutive step alone (compute_stress_from_F_trial, utils.py:13-54) on n
  * particles: F_trial[n*9], mu[n], lam[n], yield[n] (updated in place for
  * metal) -> F[n*9] (return-mapped), tau[n*9] (symmetrised Kirchhoff stress).
- * material: GSMPM_MAT_*, or 4 = jelly with FCR (F3 fixed), or 5 = the cohesive
- * fluid of fluid_return_mapping (constitutive_models.py:142-213; defined but
- * never dispatched by the reference) with StVK stress.  Test entry point. */
+ * material: GSMPM_MAT_* (5 = GSMPM_MAT_FLUID, at plastic_viscosity 0.008), or
+ * 4 = jelly with FCR (F3 fixed).  Test entry point. */
 int gsmpm_constitutive(int32_t material, const float* F_trial, int32_t n, const float* mu, const float* lam,
                        float* yield, float dt, float* F_out, float* tau_out, void* stream);
 /* The same with a material value per row (material[n], read as mixed mode
- * reads it); jelly_fcr != 0: the `else` rows take FCR.  yield is written for
- * metal rows only.  Test entry point of the mixed dispatch. */
+ * reads it, == 5 fluid included); jelly_fcr != 0: the `else` rows take FCR.
+ * yield is written for metal rows only.  Test entry point of the mixed dispatch. */
 int gsmpm_constitutive_mixed(const float* material, const float* F_trial, int32_t n, const float* mu,
                              const float* lam, float* yield, float dt, int32_t jelly_fcr, float* F_out,
                              float* tau_out, void* stream);
