@@ -631,12 +631,6 @@ __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.z += b.z;
   a.w += b.w;
 }
-// the further chunks of covering tiles with several (tiles of > 256
-// particles: a few in the 100k lego frame, most of the 240k one's).  The
-// second chunks of the 8 covering tiles are read in batches of 4 (a batch's
-// loads in flight together, the zero slot for a tile without one), then the third and
-// later ones (tiles of > 512 particles) one by one.  Until round 5 every extra
-// chunk was a load and its wait inside the loop: one round trip each.
 // one dword a lane, global -> LDS (LDS-DMA): lane l's word lands at
 // lds_base + 4 l (lds_base wave-uniform), tracked by vmcnt like a load
 __device__ __forceinline__ void glds4(const int* src, int* lds_base) {
@@ -649,37 +643,72 @@ __device__ __forceinline__ void glds4(const int* src, int* lds_base) {
 __device__ __forceinline__ float4 ld_slot(const float4* __restrict__ slots, int off) {
   return *(const float4*)((const char*)slots + (unsigned)off * 16u);
 }
-#ifndef GSMPM_EXTRA_BATCH
-#define GSMPM_EXTRA_BATCH 4
+// The further chunks of covering tiles with several (tiles of > 256 particles:
+// a lego scene at rest holds three quarters of its particles in tiles of 4-6
+// chunks, profiles/chunk_hist/).  A node's remaining window loads form one
+// ordered stream: the second chunks of its multi-chunk covers, e ascending,
+// then for e ascending chunks 2 .. nc - 1 of cover e -- the order of the sum
+// since round 5, minus the terms that were reads of the zero slot (an exact
+// + 0 on a sum that is never -0, so every node's sum keeps its bits).  The
+// stream is issued in batches of 8, a batch's loads in flight together (what
+// the first chunks' batch already holds in VGPRs; 16 in flight spilled), and
+// summed in stream order.  Until this form the second chunks went out as two
+// batches of 4, most of them to the zero slot, and every later chunk was a
+// load and its wait: a corner node of four 5-chunk tiles waited for 1 + 2 + 12
+// dependent trips to slots that k_fused wrote through from other XCDs, where
+// it now waits for 1 + 2.
+// Per lane the stream is a list of runs (bit e of `runs`: cover e's second
+// chunk; bit 8 + e: its chunks 2 .. nc - 1, when nc > 2) walked with two slot
+// offsets {cur, end}: the next load is at cur, a chunk further each time, and
+// a run that reaches end takes the next set bit (the cover's offsets again
+// from the LDS cover table, as before: nothing of node_reads stays live).  The loop is
+// wave-uniform -- it runs while any lane has a load left, the wave's maximum
+// of ceil(remaining / 8) trips, at most 8 x the largest chunk count -- and a
+// lane that is done reads the zero slot.  A wave without a multi-chunk cover
+// never enters (the caller's wave-uniform guard).
+#ifndef GSMPM_STREAM_BATCH
+#define GSMPM_STREAM_BATCH 8
 #endif
-constexpr int kExtraBatch = GSMPM_EXTRA_BATCH;  // second-chunk loads in flight (8: VGPR spills)
+constexpr int kStreamBatch = GSMPM_STREAM_BATCH;  // loads of the stream in flight together (A/B)
 __device__ __forceinline__ void node_extra(const float4* __restrict__ slots, const int* s_cov, int l0,
                                            int l1, int l2, int extra2, int zero, float4& acc) {
-  // (the offsets recomputed from the LDS cover table: keeping node_reads'
-  // 8 offsets live across the first batch spilled VGPRs)
-  int o2[8];
+  int runs = extra2;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     int ci, loc;
     node_cover(l0, l1, l2, e, ci, loc);
-    o2[e] = ((extra2 >> e) & 1) ? (s_cov[2 * ci] + 1) * kFWin + loc : zero;
+    runs |= (((extra2 >> e) & 1) & (s_cov[2 * ci + 1] > 2)) << (8 + e);
   }
+  // (one VGPR across the batches instead of l0, l1, l2: the node's offset in
+  // its own tile's window and its three sections, two bits each)
+  const int sec0 = l0 < 3 ? -1 : (l0 == kFT0 - 1 ? 1 : 0);
+  const int sec1 = l1 < 3 ? -1 : (l1 == kFT1 - 1 ? 1 : 0);
+  const int sec2 = l2 < 3 ? -1 : (l2 == kFT2 - 1 ? 1 : 0);
+  const int key = slot_loc(l0 + 1, l1 + 1, l2 + 1) | ((sec0 & 3) << 12) | ((sec1 & 3) << 14) | ((sec2 & 3) << 16);
+  static_assert(kFWin <= (1 << 12), "node_extra: the window offset takes 12 bits of the key");
+  int cur = 0, end = 0;  // slot offsets of the run's next load and of its end
+  auto next_run = [&]() {  // (runs != 0)
+    const int r = __builtin_ctz(runs);
+    runs &= runs - 1;
+    const int a = (r & 4) ? (int)((unsigned)key << 18) >> 30 : 0, b = (r & 2) ? (int)((unsigned)key << 16) >> 30 : 0,
+              c = (r & 1) ? (int)((unsigned)key << 14) >> 30 : 0;
+    const int ci = (a + 1) * 9 + (b + 1) * 3 + (c + 1);
+    const int loc = (key & 0xfff) - slot_loc(a * kFT0, b * kFT1, c * kFT2);
+    const int c0 = s_cov[2 * ci], nc = s_cov[2 * ci + 1];
+    cur = (c0 + (r < 8 ? 1 : 2)) * kFWin + loc;
+    end = (c0 + (r < 8 ? 2 : nc)) * kFWin + loc;
+  };
+  if (runs) next_run();
+  while (__builtin_amdgcn_ballot_w64(cur < end)) {
+    float4 u[kStreamBatch];
 #pragma unroll
-  for (int h = 0; h < 8; h += kExtraBatch) {
-    float4 u[kExtraBatch];
+    for (int j = 0; j < kStreamBatch; ++j) {
+      u[j] = ld_slot(slots, cur < end ? cur : zero);
+      cur += kFWin;
+      if (cur >= end && runs) next_run();
+    }
 #pragma unroll
-    for (int e = 0; e < kExtraBatch; ++e) u[e] = ld_slot(slots, o2[h + e]);
-#pragma unroll
-    for (int e = 0; e < kExtraBatch; ++e) add4(acc, u[e]);
-    __builtin_amdgcn_sched_barrier(0);  // (else the batches merge: 8 in flight, and spills)
-  }
-  int extra = extra2;  // (a tile of <= 512 particles: no iteration)
-  while (extra) {
-    const int e = __builtin_ctz(extra);
-    extra &= extra - 1;
-    int ci, loc;
-    node_cover(l0, l1, l2, e, ci, loc);
-    for (int w = s_cov[2 * ci] + 2; w < s_cov[2 * ci] + s_cov[2 * ci + 1]; ++w) add4(acc, ld_slot(slots, w * kFWin + loc));
+    for (int j = 0; j < kStreamBatch; ++j) add4(acc, u[j]);
   }
 }
 
@@ -854,6 +883,15 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
       __syncthreads();
     }
     if (it == 0) stamp(3, 3);
+#ifdef GSMPM_STAMPS
+    if (it == 0 && threadIdx.x == 0) {  // the tile, its part, its own and its covers' largest chunk count
+      int ncmax = 0;
+      for (int e = 0; e < 27; ++e) ncmax = max(ncmax, s_cov[2 * e + 1]);
+      stamp_val(3, 5, (unsigned long long)T);
+      stamp_val(3, 6, (unsigned long long)(s_cov[2 * 13 + 1] | (ncmax << 16)));
+      stamp_val(3, 7, (unsigned long long)part);
+    }
+#endif
     const int i = ti * kFT0 + l0, j = tj * kFT1 + l1, k = tk * kFT2 + l2;
     if ((unsigned)i < (unsigned)ng && (unsigned)j < (unsigned)ng && (unsigned)k < (unsigned)ng) {
       const size_t idx = ((size_t)i * ng + j) * ng + k;
@@ -866,7 +904,8 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
       for (int e = 0; e < 8; ++e) v[e] = ld_slot(slots, r.off[e]);
 #pragma unroll
       for (int e = 0; e < 8; ++e) add4(a, v[e]);
-      if (r.extra) node_extra(slots, s_cov, l0, l1, l2, r.extra, tl.max_chunks * kFWin, a);
+      if (__builtin_amdgcn_ballot_w64(r.extra != 0))  // wave-uniform: a wave of single-chunk covers skips it whole
+        node_extra(slots, s_cov, l0, l1, l2, r.extra, tl.max_chunks * kFWin, a);
       if (esc) {  // the nodes an escape wrote lie in touched tiles (mark_escape_tiles); zero what was written
         const float4 e = gacc[idx];
         add4(a, e);
