@@ -356,7 +356,7 @@ struct Touch {
   unsigned char* perm;  // [max_chunks][256] lane -> particle of the chunk (lane balance, below); null: off
   int2* rcov;           // cover records per touched position (ChunkIn): an appended tile's gets the "none" flag
   const int* tpos;      // [ntiles] touched position of each tile (-1: none); null: no box publishing
-  int* rbox;            // [ntiles][kRecStride] the neighbours' stencil boxes of this substep, per touched position
+  int* rbox;            // [ntiles][kBoxStride] the neighbours' stencil boxes (box_masks), per touched position
 };
 
 // Lane balance.  A wave's LDS accesses to the chunk window (G2P's ds_read_b128
@@ -395,6 +395,25 @@ __device__ __forceinline__ void box_unpack(int b, int (&lo)[3], int (&hi)[3]) {
     lo[d] = (b >> (4 * d)) & 15;
     hi[d] = (b >> (12 + 4 * d)) & 15;
   }
+}
+// the hull of two boxes: per axis the lower lo and the higher hi
+__device__ __forceinline__ int box_hull(int a, int b) {
+  int r = 0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    r |= min((a >> (4 * d)) & 15, (b >> (4 * d)) & 15) << (4 * d);
+    r |= max((a >> (12 + 4 * d)) & 15, (b >> (12 + 4 * d)) & 15) << (12 + 4 * d);
+  }
+  return r;
+}
+// A box as a cover record holds it (k_grid_f): per-axis bit masks with bits
+// lo..hi set, {x | y << 16, z}.  Masks of several boxes OR into a superset of
+// each, which is how the chunks of a multi-chunk tile publish theirs.
+__device__ __forceinline__ int2 box_masks(int b) {
+  int lo[3], hi[3];
+  box_unpack(b, lo, hi);
+  const int mx = (2 << hi[0]) - (1 << lo[0]), my = (2 << hi[1]) - (1 << lo[1]), mz = (2 << hi[2]) - (1 << lo[2]);
+  return make_int2(mx | (my << 16), mz);
 }
 
 // Lanes 0..26: add the tiles t + a, a_d in {-1 if d in lo, 0, 1}, with some
@@ -551,7 +570,8 @@ __global__ __launch_bounds__(1024) void k_fold_tail(int* __restrict__ flags, flo
 
 // Chunk ranges and stencil boxes of the 27 tiles whose windows reach tile
 // (ti, tj, tk) -> LDS (lanes 0..26; caller syncs), in a cover record's layout:
-// s_cov[2 e] = first chunk, s_cov[2 e + 1] = chunk count, s_bx[e] = box.
+// s_cov[2 e] = first chunk, s_cov[2 e + 1] = chunk count, s_bx[e] and
+// s_bx[32 + e] = the box's masks (box_masks of the packed tile box).
 __device__ __forceinline__ void load_cover27(const ChunkIn& ck, const int* __restrict__ tbox, const FTiles& tl, int ti,
                                              int tj, int tk, int* s_cov, int* s_bx) {
   const int e = threadIdx.x;
@@ -567,7 +587,9 @@ __device__ __forceinline__ void load_cover27(const ChunkIn& ck, const int* __res
     }
     s_cov[2 * e] = c0;
     s_cov[2 * e + 1] = nc;
-    s_bx[e] = bx;
+    const int2 bm = box_masks(bx);
+    s_bx[e] = bm.x;
+    s_bx[32 + e] = bm.y;
   }
 }
 
@@ -601,13 +623,14 @@ __device__ __forceinline__ void node_reads(int max_chunks, const int* s_cov, con
   // all e), then the tests as plain bit operations: with the reads behind
   // short-circuit tests the compiler branched around each one and waited on
   // each, 8 dependent LDS round trips in front of the slot loads
-  int nc[8], bx[8], c0[8], ci[8];
+  int nc[8], bxy[8], bz[8], c0[8], ci[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int a = (e >> 2) ? sec0 : 0, b = ((e >> 1) & 1) ? sec1 : 0, c = (e & 1) ? sec2 : 0;
     ci[e] = (a + 1) * 9 + (b + 1) * 3 + (c + 1);
     nc[e] = s_cov[2 * ci[e] + 1];
-    bx[e] = s_bx[ci[e]];
+    bxy[e] = s_bx[ci[e]];
+    bz[e] = s_bx[32 + ci[e]];
     c0[e] = s_cov[2 * ci[e]];
   }
 #pragma unroll
@@ -615,10 +638,9 @@ __device__ __forceinline__ void node_reads(int max_chunks, const int* s_cov, con
     const int ax = e >> 2, ay = (e >> 1) & 1, az = e & 1;
     const int a = ax ? sec0 : 0, b = ay ? sec1 : 0, c = az ? sec2 : 0;
     const int w0 = l0 - a * kFT0 + 1, w1 = l1 - b * kFT1 + 1, w2 = l2 - c * kFT2 + 1;
-    const int q = bx[e];
-    const bool on = ((!ax) | (sec0 != 0)) & ((!ay) | (sec1 != 0)) & ((!az) | (sec2 != 0)) & (nc[e] > 0) &
-                    (w0 >= (q & 15)) & (w1 >= ((q >> 4) & 15)) & (w2 >= ((q >> 8) & 15)) &
-                    (w0 <= ((q >> 12) & 15)) & (w1 <= ((q >> 16) & 15)) & (w2 <= ((q >> 20) & 15));
+    // inside the cover's box: the node's bit of each axis mask (box_masks)
+    const int inb = ((unsigned)bxy[e] >> w0) & ((unsigned)bxy[e] >> (16 + w1)) & ((unsigned)bz[e] >> w2) & 1;
+    const bool on = ((!ax) | (sec0 != 0)) & ((!ay) | (sec1 != 0)) & ((!az) | (sec2 != 0)) & (nc[e] > 0) & (inb != 0);
     const int loc = slot_loc(w0, w1, w2);
     r.off[e] = on ? c0[e] * kFWin + loc : max_chunks * kFWin;
     r.extra |= (on & (nc[e] > 1)) ? (1 << e) : 0;
@@ -828,15 +850,15 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
   // the other buffer, so a workgroup owning several tiles (config D: ~27 a
   // launch) pays one round trip a tile (its slot loads) instead of two.  A
   // record is 64 dwords (27 {first chunk, count} pairs + the "none" flag at
-  // dword 54) and its boxes 32; lane le moves dword le of each (the boxes'
-  // upper half a harmless copy of the lower).
+  // dword 54) and its boxes 64 (the masks' x | y << 16 words at 0..26, their
+  // z words at 32..58); lane le moves dword le of each.
   __shared__ int s_rec[2][64];
   __shared__ int s_box[2][64];
   __shared__ int s_tn[2];
   // (wave 0's lanes only: the DMA writes lds_base + 4 x lane-in-wave)
   if (pre && threadIdx.x < 64) {
     glds4(reinterpret_cast<const int*>(ck.rcov) + (size_t)i0 * 2 * kRecStride + le, &s_rec[0][0]);
-    glds4(ck.rbox + (size_t)i0 * kRecStride + (le & 31), &s_box[0][0]);
+    glds4(ck.rbox + (size_t)i0 * kBoxStride + le, &s_box[0][0]);
   }
   typedef const int __attribute__((address_space(1)))* gint_p;  // global, not flat (flat loads count in lgkmcnt too)
   // (uniform words: readfirstlane keeps them in SGPRs, not three VGPRs live across the tile loop)
@@ -863,7 +885,7 @@ __global__ __launch_bounds__(kGridT) __attribute__((amdgpu_waves_per_eu(7, 8))) 
     grid_work(blockIdx.x, it + 1, gridDim.x, pn, partn);
     if (pre && pn < ntouch && threadIdx.x < 64) {  // workgroup-uniform (kGridT = 64: one wave)
       glds4(reinterpret_cast<const int*>(ck.rcov) + (size_t)pn * 2 * kRecStride + le, &s_rec[b ^ 1][0]);
-      glds4(ck.rbox + (size_t)pn * kRecStride + (le & 31), &s_box[b ^ 1][0]);
+      glds4(ck.rbox + (size_t)pn * kBoxStride + le, &s_box[b ^ 1][0]);
       if (le == 0) glds4(ck.touched + pn, &s_tn[b ^ 1]);
     }
     int* s_cov = s_rec[b];

@@ -49,8 +49,11 @@
   // (one shared lgkmcnt, argument reloads between them)
   // (all four unconditional, straight-line: an unused lane order reads
   // cbox[0] instead, selected away below)
+  // use_box bit 0: the last launch did the P2G of these bins (cbox, perm are
+  // this chunk's); bit 1: multi-chunk tiles store and publish boxes (below)
+  const bool boxed = (use_box & 1) != 0, dense_box = (use_box & 2) != 0;
   const int w0 = min((int)blockIdx.x, tl.max_chunks - 1);
-  const bool perm0 = use_box && tc.perm;
+  const bool perm0 = boxed && tc.perm;
   const int* nch_p = ck.nchunk;
   const int4* chk_p = ck.chunk;
   const int* cbx_p = tc.cbox;
@@ -64,7 +67,7 @@
   const int qv0 = ((guc_p)prm_p)[perm0 ? (size_t)w0 * 256 + threadIdx.x : 0];
   const int nch = *(gint_p)nch_p;
   int4 cr_n = make_int4(r0, r1, r2, r3);
-  int box_n = use_box ? bx0 : kFullBox;
+  int box_n = boxed ? bx0 : kFullBox;
   int q_n = perm0 ? qv0 : (int)threadIdx.x;
   for (int w = blockIdx.x; w < nch; w += gridDim.x) {
     const int4 cr = cr_n;
@@ -72,8 +75,8 @@
     if (w + (int)gridDim.x < nch) {  // workgroup-uniform; chunk w + grid is only ever touched by this workgroup
       const int wn = w + gridDim.x;
       cr_n = ck.chunk[wn];
-      box_n = use_box ? tc.cbox[wn] : kFullBox;
-      q_n = (use_box && tc.perm) ? (int)tc.perm[(size_t)wn * 256 + threadIdx.x] : (int)threadIdx.x;
+      box_n = boxed ? tc.cbox[wn] : kFullBox;
+      q_n = (boxed && tc.perm) ? (int)tc.perm[(size_t)wn * 256 + threadIdx.x] : (int)threadIdx.x;
     }
     const int t = cr.x, first = cr.y, cnt = cr.z;
     const int k = threadIdx.x;
@@ -524,12 +527,33 @@
               ((31 - __builtin_clz(My)) << 16) | ((31 - __builtin_clz(Mz)) << 20);
       else
         box = 0;
+      const bool multi = (cr.w & 8) != 0;  // the tile has several chunks
       if (k == 0) {
         tc.cbox[w] = box;
-        rare->tbox[t] = (cr.w & 8) ? kFullBox : box;  // tiles with several chunks: whole windows
+        rare->tbox[t] = multi ? kFullBox : box;  // tile tables: whole windows (outside its box a slot holds +0)
       }
-      if (tpos_e >= 0) rare->rbox[(size_t)tpos_e * kRecStride + k] = (cr.w & 8) ? kFullBox : box;
-      if (cr.w & 8) box = kFullBox;
+      // The box as per-axis hull masks into the 27 cover records that see the
+      // tile.  A single-chunk tile's chunk stores its own, exact every substep.
+      // The chunks of a multi-chunk tile cannot agree on one box inside a
+      // launch: each ORs its own in, so the record holds a superset of every
+      // chunk's box since the re-binning zeroed it (write_cover_record) --
+      // a stale bit costs k_grid_f a load of +0, never a result.
+      if (tpos_e >= 0) {
+        int* rb = rare->rbox + (size_t)tpos_e * kBoxStride + k;
+        const int2 bm = box_masks(multi && !dense_box ? kFullBox : box);
+        if (multi && dense_box) {
+          atomicOr(rb, bm.x);
+          atomicOr(rb + 32, bm.y);
+        } else {
+          rb[0] = bm.x;
+          rb[32] = bm.y;
+        }
+      }
+      // A multi-chunk tile's chunk stores the hull of its last box and this
+      // one (the part outside the new box as +0 from the zeroed accumulators),
+      // so outside the box it stored last its slot always holds +0; the whole
+      // window on new bins (cbox is kFullBox: the slot was another chunk's)
+      if (multi) box = dense_box ? box_hull(cbox, box) : kFullBox;
       int ebits;
       frexpf(bmax, &ebits);
       const int S = bmax > 0.f ? 50 - ebits : 0;  // see k_p2g

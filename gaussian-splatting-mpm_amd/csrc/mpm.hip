@@ -1099,10 +1099,14 @@ struct ChunkOut {
   int* touched;        // [ntiles] compacted touched tiles
   int2* rcov = nullptr;  // fused pipeline: [ntiles][32] cover records per touched position (ChunkIn)
   int* tpos = nullptr;   // [ntiles] touched position of each tile, -1: none
+  int* rbox = nullptr;   // [ntiles][kBoxStride] the records' neighbour boxes, zeroed with each record written
   int td1 = 0, td2 = 0;  // tile grid (fused tiles: td0 = ntiles / (td1 td2))
 };
 
 constexpr int kRecStride = 32;  // cover-record entries per touched position (27 neighbours + the flag)
+// dwords of a record's neighbour boxes: the per-axis masks of neighbour e at
+// e (x | y << 16) and 32 + e (z), fused.h box_masks
+constexpr int kBoxStride = 64;
 // the cover record of touched tile t (position rk) from the binning's per-tile
 // first chunks / offsets in LDS (k_finish_bins)
 __device__ __forceinline__ void write_cover_record(const ChunkOut& co, int ntiles, int E, int t, int rk,
@@ -1118,6 +1122,10 @@ __device__ __forceinline__ void write_cover_record(const ChunkOut& co, int ntile
       r = make_int2(s_aux[u] & 0xffff, (cnt + kChunk - 1) / kChunk);
     }
     co.rcov[(size_t)rk * kRecStride + e] = r;
+    // the neighbour's box masks start empty: k_fused stores or ORs them in
+    // every substep, and nothing else clears them until the next binning
+    co.rbox[(size_t)rk * kBoxStride + e] = 0;
+    co.rbox[(size_t)rk * kBoxStride + 32 + e] = 0;
   }
   co.rcov[(size_t)rk * kRecStride + 27] = make_int2(0, 0);
 }
@@ -1770,7 +1778,7 @@ struct FusedBufs {
   int* cbox[2] = {nullptr, nullptr};     // [max_chunks] per-chunk stencil boxes (fused.h)
   int* tbox[2] = {nullptr, nullptr};     // [ntiles] per-tile stencil boxes
   int2* rcov[2] = {nullptr, nullptr};    // [ntiles][kRecStride] cover records per touched position (k_grid_f)
-  int* rbox[2] = {nullptr, nullptr};     // [ntiles][kRecStride] their neighbours' stencil boxes (k_fused writes)
+  int* rbox[2] = {nullptr, nullptr};     // [ntiles][kBoxStride] their neighbours' stencil boxes (k_fused writes)
   int* tpos[2] = {nullptr, nullptr};     // [ntiles] touched position of each tile (0xff bytes, -1: not touched)
   unsigned char* perm[2] = {nullptr, nullptr};  // [max_chunks][256] lane balance (fused.h)
   int4* pchunk[2] = {nullptr, nullptr};  // [max_chunks] chunk records in the balanced order (k_fused reads these)
@@ -1875,6 +1883,11 @@ struct gsmpm_mpm {
   bool lane_balance = true;               // GSMPM_LANE_BALANCE=0 turns it off (A/B)
   bool fuse_permute = true;               // GSMPM_FUSE_PERMUTE=0: separate k_permute (A/B)
   bool cover_records = true;              // GSMPM_COVER_RECORDS=0: k_grid_f reads the tile tables only (A/B)
+  // Multi-chunk tiles' chunks store the hull of their last and their new box
+  // and OR that box into the cover records (fused_body.inc); GSMPM_DENSE_BOX=0:
+  // whole windows and full masks (A/B).  Never on a FOLD handle, whose two
+  // slot buffers alternate against one box per chunk.
+  bool dense_box = true;
   int fused_wgs = 1024;                   // k_fused grid cap: the workgroups resident at once x rounds of full chunks, <= 6 (init)
   // Chunk order (k_chunk_order): k_fused's workgroup b takes the chunk at
   // position b of a size-balanced order (fu.pchunk) instead of chunk b, so
@@ -2068,6 +2081,7 @@ static ChunkOut chunk_out_f(gsmpm_mpm* h, int c) {
   ChunkOut co = chunk_out(h->fu.b[c]);
   co.rcov = h->fu.rcov[c];
   co.tpos = h->fu.tpos[c];
+  co.rbox = h->fu.rbox[c];
   co.td1 = h->ftl.td1;
   co.td2 = h->ftl.td2;
   return co;
@@ -2538,13 +2552,14 @@ struct FusedLaunch {
 template <int MAT, int MODE>
 static void launch_fused_t(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, const hipEvent_t* ev) {
   const int xlo = h->slab ? h->s_lo - h->s_margin : INT_MIN, xhi = h->slab ? h->s_hi + h->s_margin : INT_MAX;
+  const int use_box = f.use_box | (h->dense_box && !h->fold ? 2 : 0);  // bit 1: dense boxes (k_fused gains no argument)
   if constexpr (MAT == kMatMixed)
     launch(ev, k_fused_mixed<MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
-           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
+           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
            xlo, xhi, (const FusedRare*)(h->fu.rare_dev + f.c * kRareSlots + f.slot), f.mask_prev, mat_ids_of(h));
   else
     launch(ev, k_fused<MAT, MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
-           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, f.use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
+           chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
            xlo, xhi, (const FusedRare*)(h->fu.rare_dev + f.c * kRareSlots + f.slot), f.mask_prev);
 }
 template <int MODE>
@@ -3170,6 +3185,7 @@ int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
   if (const char* gc = std::getenv("GSMPM_GRAPH_COPIES")) h->graph_copies = std::max(1, std::atoi(gc));
   if (const char* fp = std::getenv("GSMPM_FUSE_PERMUTE")) h->fuse_permute = fp[0] != '0';
   if (const char* cr = std::getenv("GSMPM_COVER_RECORDS")) h->cover_records = cr[0] != '0';
+  if (const char* db = std::getenv("GSMPM_DENSE_BOX")) h->dense_box = db[0] != '0';
   {
     int dev = 0, ncu = 0, per_cu = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -3222,7 +3238,7 @@ int gsmpm_mpm_create(const gsmpm_mpm_params* prm, gsmpm_mpm** out) {
       GSMPM_TRY(alloc(h, &f.pchunk[c], mc, kMemFused, kFillZero), "ordered chunks");
       GSMPM_TRY(alloc(h, &f.tbox[c], nt, kMemFused), "boxes");
       GSMPM_TRY(alloc(h, &f.rcov[c], kRecStride * nt, kMemFused, kFillZero), "cover records");
-      GSMPM_TRY(alloc(h, &f.rbox[c], kRecStride * nt, kMemFused, kFillZero), "cover boxes");
+      GSMPM_TRY(alloc(h, &f.rbox[c], kBoxStride * nt, kMemFused, kFillZero), "cover boxes");
       GSMPM_TRY(alloc(h, &f.tpos[c], nt, kMemFused, kFillOnes), "touched positions");
       GSMPM_TRY(alloc(h, &f.perm[c], mc * 256, kMemFused, kFillZero), "lane balance");
     }

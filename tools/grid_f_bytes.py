@@ -3,12 +3,13 @@ per-source byte model ... check it against FETCH_SIZE / WRITE_SIZE").
 
 Rebuilds, on the CPU, what one lego substep hands to k_grid_f -- the tiles
 (8x8x7 cells) and their <= 256-particle chunks, each chunk's stencil box in
-window coordinates (multi-chunk tiles publish whole windows), the touched
+window coordinates (a multi-chunk tile's record holds the union of its chunks'
+boxes; --dense full: whole windows, GSMPM_DENSE_BOX=0), the touched
 tiles (tiles with particles and their upper neighbours, whose low nodes the
 stencils reach) -- and replays the kernel's reads in its own order: seven
 one-wave workgroups per touched tile, 64 owned nodes a wave, the <= 8 window
 reads of each node (zero-slot redirection outside a box), the extra chunks
-of multi-chunk tiles, the cover record (64 + 32 dwords by LDS-DMA, each
+of multi-chunk tiles, the cover record (64 + 64 dwords by LDS-DMA, each
 wave) and the v_out store.  Lines are 128 B.  Workgroup b runs on XCD b % 8,
 each XCD has its own L2, so a line is fetched from the fabric once per XCD
 that reads it (with enough L2 to keep it, ~2.5 MB a substep here).
@@ -55,6 +56,9 @@ def main():
                          "7 parts on one XCD, spatial = a tile's parts on one XCD and G consecutive touched "
                          "tiles (tile order) an XCD at a time")
     ap.add_argument("--group", type=int, default=4)
+    ap.add_argument("--dense", default="union", choices=["union", "full"],
+                    help="a multi-chunk tile's box in the cover records: the union of its chunks' stencil boxes "
+                         "(the kernel's), or the whole window (GSMPM_DENSE_BOX=0)")
     a = ap.parse_args()
     from scenarios import lego_problem
     prob = lego_problem(a.particles, a.n_grid, config=a.config)
@@ -76,7 +80,7 @@ def main():
     for t, f, c, nc, c0 in zip(tiles, first, counts, nch, cbase):
         t3 = np.array([t // (td[1] * td[2]), (t // td[2]) % td[1], t % td[2]])
         o = t3 * np.array(T) - 1
-        if nc > 1:
+        if nc > 1 and a.dense == "full":
             lo, hi = np.zeros(3, int), np.array(W) - 1
         else:
             wb = base_s[f:f + c] - o
@@ -115,11 +119,11 @@ def main():
             else:
                 xcd = (ti_pos // a.group) % 8
             wl = set()
-            # cover record (64 dwords) + boxes (32 dwords): 2 + 1 lines per wave
+            # cover record (64 dwords) + box masks (64 dwords): 2 + 2 lines per wave
             for r in ((ti_pos * 2 * 32 * 4) // LINE, (ti_pos * 2 * 32 * 4) // LINE + 1,
-                      (10**9 + ti_pos * 32 * 4) // LINE):  # (sizes as kRecStride = 32)
-                rec_xcd[xcd].add(r)
-            rec_lines_wave += 3
+                      (10**9 + ti_pos * 64 * 4) // LINE, (10**9 + ti_pos * 64 * 4) // LINE + 1):
+                rec_xcd[xcd].add(r)  # (sizes as kRecStride = 32, kBoxStride = 64)
+            rec_lines_wave += 4
             for q in range(64 * part, 64 * part + 64):
                 l0, l1, l2 = q // 56, (q // 7) % 8, q % 7
                 gi = (t3[0] * 8 + l0, t3[1] * 8 + l1, t3[2] * 7 + l2)
@@ -157,7 +161,7 @@ def main():
         "workload": {"config": a.config, "particles": int(len(x)), "n_grid": ng},
         "map": a.map if a.map != "spatial" else f"spatial, {a.group} tiles an XCD at a time",
         "tiles_with_particles": len(tinfo), "touched_tiles": len(touched), "chunks": max_chunks,
-        "multi_chunk_tiles": int((nch > 1).sum()),
+        "multi_chunk_tiles": int((nch > 1).sum()), "dense_box": a.dense,
         "algorithmic_MB": {"live_cover_reads_16B": round(live_reads * 16 / 1e6, 3),
                             "v_out_store_16B": round(stored * 16 / 1e6, 3)},
         "slot_fetch_MB": {"wave": mb(lines_wave), "xcd": mb(sum(len(s) for s in xcd_lines)), "global": mb(len(glob))},

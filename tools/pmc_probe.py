@@ -1,5 +1,6 @@
 """GPU diagnostic for rocprofv3 --pmc passes: one eager lego frame (NSUB
-substeps, re-binning launches included) and, with RENDER=1, postprocess +
+substeps, re-binning launches included; after FRAMES frames through the
+captured graphs, default none) and, with RENDER=1, postprocess +
 world outputs + two rasterizer forwards of that frame."""
 import os
 import sys
@@ -26,7 +27,11 @@ dev = torch.device('cuda:0')
 scene = bench.build_scene(A, dev)
 sim, specs = bench.make_sim(scene, dev)
 sa = scene['sargs']
-masks, t = substep_masks(specs, 0.0, sa.substep_dt, int(os.environ.get('NSUB', 100)))
+t = 0.0
+for _ in range(int(os.environ.get('FRAMES', 0))):  # FRAMES=13: the lego scene at rest before the profiled substeps
+    masks, t = substep_masks(specs, t, sa.substep_dt, sa.steps_per_frame)
+    sim.step(sa.substep_dt, masks)
+masks, t = substep_masks(specs, t, sa.substep_dt, int(os.environ.get('NSUB', 100)))
 sim.profile(sa.substep_dt, masks)
 if os.environ.get('RENDER') == '1':
     sim.postprocess()

@@ -5,7 +5,8 @@
 Each pass dir holds rocprofv3's run_counter_collection.csv from a separate
 `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` run (never combined with tracing).
 Counters are in KiB; FETCH_SIZE is doubled (MI355X_MICROARCH.md, HBM: on gfx950
-it reports half the bytes of a wide streaming read).  Averages per dispatch.
+it reports half the bytes of a wide streaming read).  Averages per dispatch
+(LAST=n in the environment: over each kernel's last n dispatches).
 """
 import collections
 import csv
@@ -33,6 +34,9 @@ def per_dispatch(path, counter):
         k = kernel_key(r["Kernel_Name"])
         if k:
             acc[k][r["Dispatch_Id"]] += float(r["Counter_Value"])
+    last = int(os.environ.get("LAST", 0))  # LAST=n: the last n dispatches of each kernel only (a warmed-up state)
+    if last:
+        acc = {k: {i: v[i] for i in sorted(v, key=int)[-last:]} for k, v in acc.items()}
     return {k: sum(v.values()) / len(v) for k, v in acc.items()}
 
 

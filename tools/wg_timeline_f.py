@@ -13,10 +13,12 @@ dev = torch.device('cuda:0')
 scene = bench.build_scene(A, dev)
 sim, specs = bench.make_sim(scene, dev)
 sa = scene['sargs']
-masks, t = substep_masks(specs, 0.0, sa.substep_dt, 300)
-sim.step(sa.substep_dt, masks[:100]); sim.step(sa.substep_dt, masks[100:200])
+frames = int(os.environ.get('FRAMES', 2))  # FRAMES=13: the scene at rest (profiles/chunk_hist/)
+masks, t = substep_masks(specs, 0.0, sa.substep_dt, 100 * frames + 100)
+for f in range(frames):
+    sim.step(sa.substep_dt, masks[100 * f:100 * f + 100])
 print('stats', sim.debug_stats(), 'pipeline', sim.pipeline)
-ms = sim.profile(sa.substep_dt, masks[200:203])  # K(P2G), grid, K, grid, K, grid, K(G2P)
+ms = sim.profile(sa.substep_dt, masks[100 * frames:100 * frames + 3])  # K(P2G), grid, K, grid, K, grid, K(G2P)
 print('event ms K/grid/bins per 3 substeps', ms)
 buf = np.zeros((4, 8192, 8), np.uint64)
 LIB.gsmpm_debug_stamps(buf.ctypes.data_as(ctypes.c_void_p), stream_of(dev))
