@@ -517,8 +517,8 @@ constexpr bool kBinAgg = GSMPM_BIN_AGG != 0;
 // The kernel's body is fused_body.inc, included by its two entry points:
 // k_fused<MAT, MODE> (one material: the symbols, arguments and code of the
 // uniform scenes, unchanged) and k_fused_mixed<MODE> (MAT = 6, the
-// per-particle ids as one more argument).  It reads the arguments, MAT, MODE
-// and `mi` by name.
+// per-particle ids as one more argument), and by their driver entry points
+// below.  It reads the arguments, MAT, MODE, `mi`, DRV and `ds` by name.
 // bin: 1 = re-bin the particles by their new x into rare->bo; 2 = zero
 // rare->bo's counts and flags for the next launch's re-binning (at the end)
 template <int MAT, int MODE>
@@ -528,6 +528,8 @@ __global__ __launch_bounds__(256, 3) void k_fused(Particles ps, GridDims g, FTil
                                                const FusedRare* __restrict__ rare, uint32_t mask_prev) {
   static_assert(MAT != kMatMixed, "the mixed dispatch is k_fused_mixed");
   const MatIds<MAT> mi{};
+  constexpr bool DRV = false;
+  const DrvSel<DRV> ds{};
 #define GSMPM_FUSED_BODY_INCLUDER
 #include "fused_body.inc"
 #undef GSMPM_FUSED_BODY_INCLUDER
@@ -542,6 +544,42 @@ __global__ __launch_bounds__(256, 3) void k_fused_mixed(Particles ps, GridDims g
                                                      const FusedRare* __restrict__ rare, uint32_t mask_prev,
                                                      MatIds<kMatMixed> mi) {
   constexpr int MAT = kMatMixed;
+  constexpr bool DRV = false;
+  const DrvSel<DRV> ds{};
+#define GSMPM_FUSED_BODY_INCLUDER
+#include "fused_body.inc"
+#undef GSMPM_FUSED_BODY_INCLUDER
+}
+
+// The driver entry points (gsmpm_mpm_add_driver; P2G modes 2 and 3, never
+// FOLD): the same body with the particle drivers after the impulse kick, the
+// selection as one more argument.  Launched only by a handle that holds a
+// driver; every other handle launches the symbols above.
+template <int MAT, int MODE>
+__global__ __launch_bounds__(256, 3) void k_fused_drv(Particles ps, GridDims g, FTiles tl, ChunkIn ck, Touch tc,
+                                                      int bin, int use_box, const float4* __restrict__ gvel,
+                                                      uint32_t mask, float dt, MatConsts mc,
+                                                      float4* __restrict__ slots, int xlo, int xhi,
+                                                      const FusedRare* __restrict__ rare, uint32_t mask_prev,
+                                                      DrvSel<true> ds) {
+  static_assert(MAT != kMatMixed, "the mixed dispatch is k_fused_mixed_drv");
+  static_assert((MODE & 2) != 0 && (MODE & 4) == 0, "drivers act in the P2G half of the unfolded pipeline");
+  const MatIds<MAT> mi{};
+  constexpr bool DRV = true;
+#define GSMPM_FUSED_BODY_INCLUDER
+#include "fused_body.inc"
+#undef GSMPM_FUSED_BODY_INCLUDER
+}
+template <int MODE>
+__global__ __launch_bounds__(256, 3) void k_fused_mixed_drv(Particles ps, GridDims g, FTiles tl, ChunkIn ck, Touch tc,
+                                                            int bin, int use_box, const float4* __restrict__ gvel,
+                                                            uint32_t mask, float dt, MatConsts mc,
+                                                            float4* __restrict__ slots, int xlo, int xhi,
+                                                            const FusedRare* __restrict__ rare, uint32_t mask_prev,
+                                                            MatIds<kMatMixed> mi, DrvSel<true> ds) {
+  static_assert((MODE & 2) != 0 && (MODE & 4) == 0, "drivers act in the P2G half of the unfolded pipeline");
+  constexpr int MAT = kMatMixed;
+  constexpr bool DRV = true;
 #define GSMPM_FUSED_BODY_INCLUDER
 #include "fused_body.inc"
 #undef GSMPM_FUSED_BODY_INCLUDER

@@ -1,6 +1,7 @@
 // fused_body.inc -- the body of k_fused<MAT, MODE> and k_fused_mixed<MODE>
-// (fused.h), included inside both kernels: it reads their arguments, MAT,
-// MODE and the material ids `mi` by name.
+// (fused.h), included inside both kernels and their driver entry points: it
+// reads their arguments, MAT, MODE, the material ids `mi`, DRV and the
+// drivers' selection `ds` by name.
 #ifndef GSMPM_FUSED_BODY_INCLUDER
 #error "fused_body.inc is the body of k_fused / k_fused_mixed: it is included inside those two kernels in fused.h only"
 #endif
@@ -387,6 +388,8 @@
             }
           }
         }
+        // the particle drivers (gsmpm_mpm_add_driver), after the impulses
+        if constexpr (DRV) apply_drivers(ds, static_cast<const BcTable*>(rare->bct), mask, p, x, m, v);
         // compute_stress_from_F_trial (utils.py:13-54)
         if constexpr (MAT == kMatMixed) {
           // the per-particle dispatch (constitutive.h).  The returned F is

@@ -144,11 +144,12 @@ __device__ __forceinline__ int tile_of(const float (&x)[3], const GridDims& g, c
 
 // ------------------------------------------------------- particle front --
 // loads + ImpulseBC.apply + compute_stress_from_F_trial for one particle
-template <int MAT>
+// DRV (the driver entry points): the particle drivers follow the impulses
+template <int MAT, bool DRV = false>
 __device__ __forceinline__ void particle_front(const Particles& ps, int p, const BcTable* __restrict__ bct,
                                                uint32_t mask, float dt, const MatConsts& mc, const MatIds<MAT>& mi,
                                                float (&x)[3], float (&v)[3], float (&C)[3][3], float& m,
-                                               float (&nvt)[3][3]) {
+                                               float (&nvt)[3][3], const DrvSel<DRV>& ds = DrvSel<DRV>{}) {
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     x[d] = ps.ld(PX + d, p);
@@ -172,6 +173,7 @@ __device__ __forceinline__ void particle_front(const Particles& ps, int p, const
       }
     }
   }
+  if constexpr (DRV) apply_drivers(ds, bct, mask, p, x, m, v);
   // compute_stress_from_F_trial (utils.py:13-54), fused: stress never leaves registers
 #pragma unroll
   for (int i = 0; i < 9; ++i) nvt[i / 3][i % 3] = 0.f;
@@ -461,6 +463,8 @@ __global__ __launch_bounds__(256) void k_p2g(Particles ps, GridDims g, Tiles tl,
                                              int* __restrict__ nonfin) {
   static_assert(MAT != kMatMixed, "the mixed dispatch is k_p2g_mixed");
   const MatIds<MAT> mi{};
+  constexpr bool DRV = false;
+  const DrvSel<DRV> ds{};
 #define GSMPM_P2G_BODY_INCLUDER
 #include "p2g_body.inc"
 #undef GSMPM_P2G_BODY_INCLUDER
@@ -472,6 +476,35 @@ __global__ __launch_bounds__(256) void k_p2g_mixed(Particles ps, GridDims g, Til
                                                    MatConsts mc, float4* __restrict__ slots, float4* __restrict__ gacc,
                                                    int* __restrict__ nonfin, MatIds<kMatMixed> mi) {
   constexpr int MAT = kMatMixed;
+  constexpr bool DRV = false;
+  const DrvSel<DRV> ds{};
+#define GSMPM_P2G_BODY_INCLUDER
+#include "p2g_body.inc"
+#undef GSMPM_P2G_BODY_INCLUDER
+}
+
+// The driver entry points (gsmpm_mpm_add_driver): the same body with the
+// particle drivers in its front, the selection as one more argument.
+// Launched only by a handle that holds a driver.
+template <int MAT>
+__global__ __launch_bounds__(256) void k_p2g_drv(Particles ps, GridDims g, Tiles tl, ChunkIn ck,
+                                                 const BcTable* __restrict__ bct, uint32_t mask, float dt,
+                                                 MatConsts mc, float4* __restrict__ slots, float4* __restrict__ gacc,
+                                                 int* __restrict__ nonfin, DrvSel<true> ds) {
+  static_assert(MAT != kMatMixed, "the mixed dispatch is k_p2g_mixed_drv");
+  const MatIds<MAT> mi{};
+  constexpr bool DRV = true;
+#define GSMPM_P2G_BODY_INCLUDER
+#include "p2g_body.inc"
+#undef GSMPM_P2G_BODY_INCLUDER
+}
+__global__ __launch_bounds__(256) void k_p2g_mixed_drv(Particles ps, GridDims g, Tiles tl, ChunkIn ck,
+                                                       const BcTable* __restrict__ bct, uint32_t mask, float dt,
+                                                       MatConsts mc, float4* __restrict__ slots,
+                                                       float4* __restrict__ gacc, int* __restrict__ nonfin,
+                                                       MatIds<kMatMixed> mi, DrvSel<true> ds) {
+  constexpr int MAT = kMatMixed;
+  constexpr bool DRV = true;
 #define GSMPM_P2G_BODY_INCLUDER
 #include "p2g_body.inc"
 #undef GSMPM_P2G_BODY_INCLUDER
@@ -1503,6 +1536,27 @@ __global__ __launch_bounds__(256) void k_region_material(Particles ps, const int
   if (in_region(ps, p, b)) mat[orig[p]] = material;
 }
 
+// ----------------------------------------------------- particle drivers --
+// The selection of driver j (gsmpm_mpm_add_driver), bit j of the caller-order
+// words: the rows inside the box now, or the rows of the caller's byte mask.
+// Each word has one writer (orig is a permutation), and bit j was never set.
+__global__ __launch_bounds__(256) void k_driver_select_box(Particles ps, const int* __restrict__ orig, RegionBox b,
+                                                           int j, uint32_t* __restrict__ sel) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= ps.n) return;
+  if (in_region(ps, p, b)) sel[orig[p]] |= 1u << j;
+}
+__global__ __launch_bounds__(256) void k_driver_select_mask(const uint8_t* __restrict__ mask, int n, int j,
+                                                            uint32_t* __restrict__ sel) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && mask[i]) sel[i] |= 1u << j;
+}
+__global__ __launch_bounds__(256) void k_driver_get(const uint32_t* __restrict__ sel, int n, int j,
+                                                    uint8_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint8_t)((sel[i] >> j) & 1u);
+}
+
 // MaterialParamsModifier.apply / applymu (boundary_conditions.py:57-70) as the
 // reference means them: E, nu and density of the rows inside become mu, lam
 // and mass the way k_init makes them, then mu takes the override
@@ -1812,6 +1866,10 @@ struct gsmpm_mpm {
   // whether the P2G kernels run the mixed instantiation (until set_particles)
   float* mat_ids = nullptr;
   bool mixed = false;
+  // particle drivers (gsmpm_mpm_add_driver): their selection words [np] in
+  // caller order, allocated with the first driver; host_bc.n_drv > 0 selects
+  // the driver entry points of the P2G kernels (has_drivers)
+  uint32_t* drv_sel = nullptr;
   bool rebin_set = false;  // the re-binning interval was set by the caller (it survives a mode change)
   int n = 0, np = 0;
   float* planes = nullptr;
@@ -2065,6 +2123,16 @@ static MatIds<kMatMixed> mat_ids_of(gsmpm_mpm* h) {
   return MatIds<kMatMixed>{h->mat_ids, h->orig, (h->prm.flags & GSMPM_FLAG_JELLY_FCR) ? 4 : 0};
 }
 
+// Particle drivers select the driver entry points of the P2G kernels
+// (k_fused_drv, k_p2g_drv and their mixed forms); a handle without one
+// launches the plain ones, with the arguments they always had.
+static bool has_drivers(const gsmpm_mpm* h) { return h->host_bc.n_drv > 0; }
+static DrvSel<true> drv_sel_of(gsmpm_mpm* h) {
+  uint32_t bits = 0;
+  for (int j = 0; j < h->host_bc.n_drv; ++j) bits |= 1u << h->host_bc.drv[j].bit;
+  return DrvSel<true>{h->drv_sel, h->orig, bits};
+}
+
 // the chunk records k_fused walks: the balanced order (k_chunk_order) or tile order
 static int4* fused_records(gsmpm_mpm* h, int c) {
   return h->chunk_order ? h->fu.pchunk[c] : h->fu.b[c].chunk;
@@ -2115,6 +2183,16 @@ static void launch(const hipEvent_t* ev, F kernel, dim3 grid, dim3 block, hipStr
 
 template <int MAT>
 static void launch_p2g(gsmpm_mpm* h, int c, uint32_t mask, float dt, hipStream_t st, const hipEvent_t* ev) {
+  if (has_drivers(h)) {
+    if constexpr (MAT == kMatMixed)
+      launch(ev, k_p2g_mixed_drv, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
+             (const BcTable*)h->dev_bc, mask, dt, h->mc, h->ph.slots, h->gacc, h->nonfin_dev, mat_ids_of(h),
+             drv_sel_of(h));
+    else
+      launch(ev, k_p2g_drv<MAT>, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
+             (const BcTable*)h->dev_bc, mask, dt, h->mc, h->ph.slots, h->gacc, h->nonfin_dev, drv_sel_of(h));
+    return;
+  }
   if constexpr (MAT == kMatMixed)
     launch(ev, k_p2g_mixed, dim3(p2g_grid(h)), dim3(kChunk), st, particles_of(h), h->g, h->tl, chunk_in(h, c),
            (const BcTable*)h->dev_bc, mask, dt, h->mc, h->ph.slots, h->gacc, h->nonfin_dev, mat_ids_of(h));
@@ -2553,6 +2631,20 @@ template <int MAT, int MODE>
 static void launch_fused_t(gsmpm_mpm* h, const FusedLaunch& f, hipStream_t st, const hipEvent_t* ev) {
   const int xlo = h->slab ? h->s_lo - h->s_margin : INT_MIN, xhi = h->slab ? h->s_hi + h->s_margin : INT_MAX;
   const int use_box = f.use_box | (h->dense_box && !h->fold ? 2 : 0);  // bit 1: dense boxes (k_fused gains no argument)
+  if constexpr ((MODE & 2) != 0 && (MODE & 4) == 0) {  // drivers act in the P2G half; a FOLD handle holds none
+    if (has_drivers(h)) {
+      const FusedRare* rare = h->fu.rare_dev + f.c * kRareSlots + f.slot;
+      if constexpr (MAT == kMatMixed)
+        launch(ev, k_fused_mixed_drv<MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
+               chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc,
+               f.slots, xlo, xhi, rare, f.mask_prev, mat_ids_of(h), drv_sel_of(h));
+      else
+        launch(ev, k_fused_drv<MAT, MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
+               chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc,
+               f.slots, xlo, xhi, rare, f.mask_prev, drv_sel_of(h));
+      return;
+    }
+  }
   if constexpr (MAT == kMatMixed)
     launch(ev, k_fused_mixed<MODE>, dim3(fused_grid(h)), dim3(256), st, particles_of(h), h->g, h->ftl,
            chunk_in_f(h, f.c), touch_f(h, f.c), f.bin, use_box, (const float4*)h->gvel, f.mask, f.dt, h->mc, f.slots,
@@ -3559,6 +3651,8 @@ static void choose_rebins(gsmpm_mpm* h, float dt, int nsub, const uint32_t* bc) 
   bool imp = false;
   for (int b = 0; b < h->host_bc.n_imp && !imp; ++b)
     for (int s = 0; s < nsub && !imp; ++s) imp = !bc || ((bc[s] >> h->host_bc.imp[b].bit) & 1u);
+  for (int j = 0; j < h->host_bc.n_drv && !imp; ++j)  // an active driver sets v as freely
+    for (int s = 0; s < nsub && !imp; ++s) imp = !bc || ((bc[s] >> h->host_bc.drv[j].bit) & 1u);
   if (imp) m = std::max(m, (nsub + 4) / 5);
   h->rebin_m = std::min(std::max(m, 0), nsub);
 }
@@ -3837,6 +3931,92 @@ int gsmpm_mpm_set_region_params(gsmpm_mpm* h, const double center[3], const doub
   hipLaunchKernelGGL(k_region_params, dim3(div_up(h->n, 256)), dim3(256), 0, (hipStream_t)stream, particles_of(h),
                      region_box(center, size), logE, y, (float)density, mu_override != 1000.0 ? 1 : 0,
                      (float)mu_override);
+  GSMPM_LAUNCH_CHECK();
+  return GSMPM_OK;
+}
+
+// A particle driver (gsmpm.h).  Refused, with nothing changed, where the
+// selection could not follow its particles or no driver entry point exists: a
+// slab (migration moves rows between ranks; the selection is per caller row)
+// and the folded pipeline (GSMPM_FOLD=1), as add_collider refuses.
+int gsmpm_mpm_add_driver(gsmpm_mpm* h, const gsmpm_driver* d, const uint8_t* mask, void* stream) {
+  GSMPM_REQUIRE(h && d, "gsmpm_mpm_add_driver: null argument");
+  if (h->slab) {
+    set_error("gsmpm_mpm_add_driver: particle drivers are not supported on a slab of a multi-GPU domain "
+              "(migration moves rows between ranks and the selection does not follow)");
+    return GSMPM_ESTATE;
+  }
+  if (h->fold) {
+    set_error("gsmpm_mpm_add_driver: particle drivers are not supported by the folded pipeline (GSMPM_FOLD=1)");
+    return GSMPM_ESTATE;
+  }
+  if (!h->has_particles) {
+    set_error("gsmpm_mpm_add_driver: particles not set (the selection is taken from them)");
+    return GSMPM_ESTATE;
+  }
+  GSMPM_REQUIRE(d->kind >= GSMPM_DRIVER_PARTICLE_IMPULSE && d->kind <= GSMPM_DRIVER_ENFORCE_ROTATION,
+                "gsmpm_mpm_add_driver: unknown kind");
+  auto fin3 = [](const double* a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); };
+  Driver r{};
+  r.kind = d->kind;
+  if (d->kind == GSMPM_DRIVER_PARTICLE_IMPULSE) {
+    GSMPM_REQUIRE(fin3(d->force) && std::isfinite(d->substep_dt), "gsmpm_mpm_add_driver: non-finite force or substep_dt");
+    for (int k = 0; k < 3; ++k) r.a[k] = (float)d->force[k];
+    r.p0 = (float)d->substep_dt;
+  } else if (d->kind == GSMPM_DRIVER_ENFORCE_TRANSLATION) {
+    GSMPM_REQUIRE(fin3(d->velocity), "gsmpm_mpm_add_driver: non-finite velocity");
+    for (int k = 0; k < 3; ++k) r.a[k] = (float)d->velocity[k];
+  } else {
+    GSMPM_REQUIRE(fin3(d->point) && fin3(d->axis) && std::isfinite(d->omega) && std::isfinite(d->along),
+                  "gsmpm_mpm_add_driver: non-finite point, axis, omega or along");
+    const double nn = d->axis[0] * d->axis[0] + d->axis[1] * d->axis[1] + d->axis[2] * d->axis[2];
+    GSMPM_REQUIRE(nn > 0, "gsmpm_mpm_add_driver: zero axis");
+    const double sc = 1.0 / std::sqrt(nn);  // f64, as the plane collider's normal
+    for (int k = 0; k < 3; ++k) {
+      r.a[k] = (float)(sc * d->axis[k]);
+      r.b[k] = (float)d->point[k];
+    }
+    r.p0 = (float)d->omega;
+    r.p1 = (float)d->along;
+  }
+  if (!mask) {
+    GSMPM_REQUIRE(fin3(d->center) && fin3(d->size), "gsmpm_mpm_add_driver: non-finite box");
+    GSMPM_REQUIRE(d->size[0] > 0 && d->size[1] > 0 && d->size[2] > 0,
+                  "gsmpm_mpm_add_driver: the box size must be positive (or give a mask)");
+  }
+  const int id = add_bc_common(h);
+  if (id < 0) return GSMPM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (!h->drv_sel) {
+    const hipError_t e = alloc(h, &h->drv_sel, (size_t)h->np, kMemCommon, kFillZero);
+    if (e != hipSuccess) {
+      --h->n_bc;
+      GSMPM_HIP(e);
+    }
+    GSMPM_HIP(hipStreamSynchronize(nullptr));  // the fill ran on the null stream
+  }
+  const int j = h->host_bc.n_drv;  // n_drv <= n_bc <= kMaxBC
+  if (mask)
+    hipLaunchKernelGGL(k_driver_select_mask, dim3(div_up(h->n, 256)), dim3(256), 0, st, mask, h->n, j, h->drv_sel);
+  else
+    hipLaunchKernelGGL(k_driver_select_box, dim3(div_up(h->n, 256)), dim3(256), 0, st, particles_of(h),
+                       (const int*)h->orig, region_box(d->center, d->size), j, h->drv_sel);
+  GSMPM_LAUNCH_CHECK();
+  r.bit = id;
+  h->host_bc.drv[j] = r;
+  h->host_bc.n_drv = j + 1;
+  const int rc = upload_bc(h);  // drops the cached graphs: they baked the entry points and the driver bits
+  return rc ? rc : id;
+}
+
+int gsmpm_mpm_get_driver_selection(gsmpm_mpm* h, int32_t id, uint8_t* out, void* stream) {
+  GSMPM_REQUIRE(h && out, "gsmpm_mpm_get_driver_selection: null argument");
+  int j = -1;
+  for (int k = 0; k < h->host_bc.n_drv; ++k)
+    if (h->host_bc.drv[k].bit == id) j = k;
+  GSMPM_REQUIRE(j >= 0, "gsmpm_mpm_get_driver_selection: no driver has that bc id");
+  hipLaunchKernelGGL(k_driver_get, dim3(div_up(h->n, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint32_t*)h->drv_sel, h->n, j, out);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }

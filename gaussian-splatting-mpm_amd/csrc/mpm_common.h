@@ -82,6 +82,15 @@ struct GridOpRot {
   int idx;
   float om[3];
 };
+// A particle driver (gsmpm_mpm_add_driver): a record on a fixed selection of
+// particles, bit j of the selection words for drv[j].  kind 0 masked impulse:
+// a = force, p0 = substep_dt; 1 enforced translation: a = velocity; 2
+// enforced rotation: a = unit axis, b = point, p0 = omega, p1 = along.
+enum DriverKind : int { kDrvImpulse = 0, kDrvTranslate = 1, kDrvRotate = 2 };
+struct Driver {
+  int kind, bit;
+  float a[3], b[3], p0, p1;
+};
 struct BcTable {
   int n_imp, n_ops;
   Impulse imp[kMaxBC];
@@ -89,7 +98,54 @@ struct BcTable {
   GridOpExt ext[kMaxBC];  // parallel to op[], after it: the offsets the plain instantiations read do not move
   GridOpMov mov[kMaxBC];  // parallel again, after ext[]: read by the MOV instantiations only
   GridOpRot rot[kMaxBC];  // parallel again, after mov[]: read by the ROT instantiations only
+  // the particle drivers, last: read by the driver entry points of the P2G kernels only
+  int n_drv;
+  Driver drv[kMaxBC];
 };
+
+// The drivers' selection: the last argument of the driver entry points of the
+// P2G kernels (k_fused_drv, k_p2g_drv and their mixed forms).  Empty for the
+// plain entry points, which do not take it.  One word per particle in CALLER
+// order (bit j: drv[j] drives the row), read through the storage -> caller
+// map as MatIds reads the ids; bits: the OR of the drivers' activity bits.
+template <bool DRV>
+struct DrvSel {};
+template <>
+struct DrvSel<true> {
+  const uint32_t* sel;  // [n] caller order
+  const int* orig;      // [n] caller row of each storage row
+  uint32_t bits;
+};
+// The drivers of storage row p, in table order, after the box impulses and
+// before the stress.  Outside every driver's window the cost is the uniform
+// test mask & bits; inside one, the indirect load of the row's word and a
+// loop whose record loads are uniform (scalar).  (The empty overload only
+// lets the shared bodies name the call under their `if constexpr (DRV)`.)
+__device__ __forceinline__ void apply_drivers(const DrvSel<false>&, const BcTable*, uint32_t, int, const float (&)[3],
+                                              float, float (&)[3]) {}
+__device__ __forceinline__ void apply_drivers(const DrvSel<true>& ds, const BcTable* __restrict__ bct, uint32_t mask,
+                                              int p, const float (&x)[3], float m, float (&v)[3]) {
+  if (!(mask & ds.bits)) return;
+  const uint32_t word = ds.sel[ds.orig[p]];
+  const int nd = bct->n_drv;
+  for (int j = 0; j < nd; ++j) {
+    const Driver& dr = bct->drv[j];
+    if (!((mask >> dr.bit) & 1u)) continue;  // uniform
+    if (!((word >> j) & 1u)) continue;
+    if (dr.kind == kDrvImpulse) {  // ImpulseBC.apply's arithmetic (boundary_conditions.py:45)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) v[d] = v[d] + dr.a[d] / m * dr.p0;
+    } else if (dr.kind == kDrvTranslate) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) v[d] = dr.a[d];
+    } else {
+      const float r0 = x[0] - dr.b[0], r1 = x[1] - dr.b[1], r2 = x[2] - dr.b[2];
+      v[0] = dr.p0 * (dr.a[1] * r2 - dr.a[2] * r1) + dr.p1 * dr.a[0];
+      v[1] = dr.p0 * (dr.a[2] * r0 - dr.a[0] * r2) + dr.p1 * dr.a[1];
+      v[2] = dr.p0 * (dr.a[0] * r1 - dr.a[1] * r0) + dr.p1 * dr.a[2];
+    }
+  }
+}
 // One rotating record as k_set_poses reads it: unit axis k and |omega| in f64
 // (the angle is wm * tau in f64), the rest f32 of the caller's doubles.
 struct RotRec {

@@ -1,6 +1,7 @@
 // p2g_body.inc -- the body of k_p2g<MAT> and k_p2g_mixed (mpm.hip), included
-// inside both kernels: it reads their arguments, MAT and the material ids `mi`
-// by name.
+// inside both kernels and their driver entry points (k_p2g_drv,
+// k_p2g_mixed_drv): it reads their arguments, MAT, the material ids `mi`, DRV
+// and the drivers' selection `ds` by name.
 #ifndef GSMPM_P2G_BODY_INCLUDER
 #error "p2g_body.inc is the body of k_p2g / k_p2g_mixed: it is included inside those two kernels in mpm.hip only"
 #endif
@@ -20,7 +21,7 @@
       if (k < cnt) {
         const int p = ck.list[first + k];
         float x[3], v[3], C[3][3], m, nvt[3][3];
-        particle_front<MAT>(ps, p, bct, mask, dt, mc, mi, x, v, C, m, nvt);
+        particle_front<MAT, DRV>(ps, p, bct, mask, dt, mc, mi, x, v, C, m, nvt, ds);
         p2g_global<MAT>(x, v, C, m, nvt, g, dt, gacc);
       }
       continue;  // workgroup-uniform
@@ -33,7 +34,7 @@
     float bound = 0.f;
     if (k < cnt) {
       const int p = ck.list[first + k];
-      particle_front<MAT>(ps, p, bct, mask, dt, mc, mi, x, v, C, m, nvt);
+      particle_front<MAT, DRV>(ps, p, bct, mask, dt, mc, mi, x, v, C, m, nvt, ds);
       bspline(x, g.inv_dx, base, fx, ww, dw);
       {  // non-finite scatter inputs (the fixed-point conversion would hide them; fused.h)
         float chk = m + v[0] + v[1] + v[2];

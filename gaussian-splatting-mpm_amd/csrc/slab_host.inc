@@ -614,6 +614,11 @@ int gsmpm_mpm_slab_init(gsmpm_mpm* h, int32_t rank, int32_t world, int32_t lo, i
               "(the migration payload does not carry the ids)");
     return GSMPM_ESTATE;
   }
+  if (h->host_bc.n_drv > 0) {
+    set_error("gsmpm_mpm_slab_init: the handle holds particle drivers (gsmpm_mpm_add_driver), which slabs do not "
+              "support (migration moves rows between ranks and the selection does not follow)");
+    return GSMPM_ESTATE;
+  }
   if (h->n_ext > 0) {
     set_error("gsmpm_mpm_slab_init: the handle holds extended colliders (gsmpm_mpm_add_collider), which slabs do "
               "not support (their grid passes apply fixed cubes and plane colliders only)");

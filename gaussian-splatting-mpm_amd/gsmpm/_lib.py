@@ -59,6 +59,14 @@ class ColliderSpin(ctypes.Structure):
                 ("omega", ctypes.c_double * 3), ("pivot", ctypes.c_double * 3)]
 
 
+class Driver(ctypes.Structure):
+    """gsmpm_driver (include/gsmpm.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("center", ctypes.c_double * 3), ("size", ctypes.c_double * 3),
+                ("force", ctypes.c_double * 3), ("substep_dt", ctypes.c_double), ("velocity", ctypes.c_double * 3),
+                ("point", ctypes.c_double * 3), ("axis", ctypes.c_double * 3), ("omega", ctypes.c_double),
+                ("along", ctypes.c_double)]
+
+
 class RasterArgs(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32), ("D", ctypes.c_int32), ("M", ctypes.c_int32),
@@ -127,6 +135,8 @@ _SIGS = {
     "gsmpm_mpm_add_rotating_collider": (ctypes.c_int, [c_void_p, ctypes.POINTER(Collider),
                                                        ctypes.POINTER(ColliderSpin)]),
     "gsmpm_mpm_get_poses": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), c_void_p]),
+    "gsmpm_mpm_add_driver": (ctypes.c_int, [c_void_p, ctypes.POINTER(Driver), c_void_p, c_void_p]),
+    "gsmpm_mpm_get_driver_selection": (ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p]),
     "gsmpm_rccl_unique_id": (ctypes.c_int, [c_void_p]),
     "gsmpm_rccl_comm_init": (ctypes.c_int, [c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(c_void_p)]),
     "gsmpm_rccl_comm_destroy": (ctypes.c_int, [c_void_p]),
@@ -258,6 +268,8 @@ PIPE_PHASED, PIPE_FUSED = 0, 1
 # extended colliders (gsmpm_mpm_add_collider)
 SHAPE = {"plane": 0, "ball": 1, "box": 2, "walls": 3}
 SURFACE = {"sticky": 0, "slip": 1, "separate": 2}
+# particle drivers (gsmpm_mpm_add_driver)
+DRIVER = {"particle_impulse": 0, "enforce_particle_translation": 1, "enforce_particle_rotation": 2}
 
 
 class GsmpmError(RuntimeError):

@@ -160,6 +160,63 @@ class Simulator:
         check(LIB.gsmpm_mpm_get_poses(self._h, n, buf, stream_of(self.device)), "gsmpm_mpm_get_poses")
         return np.frombuffer(buf, dtype=np.float32, count=16 * n_rot * n).reshape(n, n_rot, 16).copy()
 
+    def add_driver(self, kind, *, center=None, size=None, mask=None, force=None, substep_dt=None, velocity=None,
+                   point=None, axis=None, omega=0.0, along=0.0) -> int:
+        """A particle driver (gsmpm_mpm_add_driver): a record on a selection of
+        particles that is chosen now and never changes -- the rows inside the
+        box ``center`` / ``size`` at this moment (strict f32 |x - c| < s), or
+        the rows of ``mask`` (n booleans, caller order).  ``kind``:
+        "particle_impulse" (``force``, ``substep_dt``: v += force / m *
+        substep_dt), "enforce_particle_translation" (``velocity``: v = velocity)
+        or "enforce_particle_rotation" (``point``, ``axis``, ``omega``,
+        ``along``: v = omega * cross(axis, x - point) + along * axis, the axis
+        normalised).  Drivers act after the box impulses, in the order they
+        were added, before the stress.  Returns the record's bit of the
+        activity mask; the caller's clock decides its window."""
+        if kind not in _lib.DRIVER:
+            raise ValueError(f"add_driver: unknown kind {kind!r} (one of {sorted(_lib.DRIVER)})")
+        want = {"particle_impulse": ("force", "substep_dt"), "enforce_particle_translation": ("velocity",),
+                "enforce_particle_rotation": ("point", "axis")}[kind]
+        given = {"force": force, "substep_dt": substep_dt, "velocity": velocity, "point": point, "axis": axis}
+        extra = [k for k, v in given.items() if v is not None and k not in want]
+        missing = [k for k in want if given[k] is None]
+        if kind != "enforce_particle_rotation" and (float(omega) != 0.0 or float(along) != 0.0):
+            extra.append("omega / along")
+        if extra or missing:
+            raise TypeError(f"add_driver: a {kind} takes {', '.join(want)}"
+                            + (f"; missing {missing}" if missing else "") + (f"; unexpected {extra}" if extra else ""))
+        if (center is None or size is None) if mask is None else (center is not None or size is not None):
+            raise TypeError("add_driver: give the selection as center and size, or as mask")
+        d = _lib.Driver()
+        d.kind = _lib.DRIVER[kind]
+        if mask is None:
+            d.center[:] = [float(a) for a in center]
+            d.size[:] = [float(a) for a in size]
+        else:
+            mask = torch.as_tensor(mask).to(self.device).reshape(-1).ne(0).to(torch.uint8).contiguous()
+            if mask.numel() != self.n:
+                raise ValueError(f"add_driver: the mask has {mask.numel()} entries for {self.n} particles")
+        if kind == "particle_impulse":
+            d.force[:] = [float(a) for a in force]
+            d.substep_dt = float(substep_dt)
+        elif kind == "enforce_particle_translation":
+            d.velocity[:] = [float(a) for a in velocity]
+        else:
+            d.point[:] = [float(a) for a in point]
+            d.axis[:] = [float(a) for a in axis]
+            d.omega, d.along = float(omega), float(along)
+        with torch.cuda.device(self.device):  # the first driver allocates the selection words
+            return check(LIB.gsmpm_mpm_add_driver(self._h, ctypes.byref(d), ptr(mask), stream_of(self.device)),
+                         "add_driver")
+
+    def driver_selection(self, bit: int) -> torch.Tensor:
+        """The selection of the driver with activity bit ``bit``: n booleans in
+        caller order (gsmpm_mpm_get_driver_selection)."""
+        out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+        check(LIB.gsmpm_mpm_get_driver_selection(self._h, int(bit), ptr(out), stream_of(self.device)),
+              "driver_selection")
+        return out.bool()
+
     def graph_count(self) -> int:
         """Step graphs the handle caches now (gsmpm_mpm_graph_count; diagnostics)."""
         return check(LIB.gsmpm_mpm_graph_count(self._h), "graph_count")

@@ -203,12 +203,72 @@ class ColliderBC:
         return time >= self.start_time and time < self.end_time
 
 
+class ParticleDriverBC:
+    """particle_impulse / enforce_particle_translation /
+    enforce_particle_rotation (not in the reference; ImpulseBC.apply's
+    "#TODO: Need to replace this with a mask", boundary_conditions.py:43, asks
+    for the first): a record on a selection of particles that is chosen once,
+    when the record is added -- the rows inside ``center`` / ``size`` at that
+    moment, or the rows of ``mask`` (n booleans, caller order) -- and never
+    changes, wherever the particles go (gsmpm_mpm_add_driver).
+
+      particle_impulse              force              v += force / m * substep_dt
+      enforce_particle_translation  velocity           v = velocity
+      enforce_particle_rotation     point, axis,       v = omega * cross(axis, x - point) + along * axis
+                                    omega, along
+
+    Active while start_time <= time < end_time on the host's float64 clock:
+    ``start_time`` (default 0) with ``end_time`` (default 999.0) or ``num_dt``
+    (end_time = start_time + substep_dt * num_dt in f64, as BasicBC).  Within
+    a substep the drivers run after every box impulse, in the order they were
+    added, before the stress: particle_preprocess with the drivers after the
+    impulses."""
+
+    _params = {"particle_impulse": ("force",), "enforce_particle_translation": ("velocity",),
+               "enforce_particle_rotation": ("point", "axis")}
+
+    def __init__(self, n_particles, bc_args, sim_args=None):
+        self.n_particles = n_particles
+        self.id = bc_args.get("id")
+        self.type = bc_args["type"]
+        if self.type not in self._params:
+            raise ValueError(f"particle driver: unknown type {self.type!r} (one of {sorted(self._params)})")
+        self.start_time = float(bc_args.get("start_time", 0.0))
+        if bc_args.get("num_dt") is not None:
+            if bc_args.get("end_time") is not None:
+                raise TypeError(f"{self.type}: give end_time or num_dt, not both")
+            self.end_time = self.start_time + sim_args.substep_dt * bc_args["num_dt"]  # f64, boundary_conditions.py:16
+        else:
+            end = bc_args.get("end_time")
+            self.end_time = 999.0 if end is None else float(end)
+        self.center, self.size, self.mask = bc_args.get("center"), bc_args.get("size"), bc_args.get("mask")
+        if (self.center is None or self.size is None) if self.mask is None else (self.center is not None
+                                                                                 or self.size is not None):
+            raise TypeError(f"{self.type}: give the selection as center and size, or as mask")
+        self.params = {k: bc_args[k] for k in self._params[self.type]}  # KeyError names the missing one
+        if self.type == "particle_impulse":
+            sdt = bc_args.get("substep_dt")
+            self.params["substep_dt"] = float(sim_args.substep_dt if sdt is None else sdt)
+            self.params["force"] = list(self.params["force"][:3])
+        elif self.type == "enforce_particle_rotation":
+            self.params["omega"] = float(bc_args.get("omega", 0.0))
+            self.params["along"] = float(bc_args.get("along", 0.0))
+        self.isCollide = False
+        self.bit = None  # library bc id (bit of the activity mask)
+
+    def isActive(self, time):
+        return time >= self.start_time and time < self.end_time
+
+
 # boundary_conditions.py:97-109 -- note preprocess_bc is a *string*, so
-# ``type in preprocess_bc`` is a substring test exactly as in the reference.
+# ``type in preprocess_bc`` is a substring test exactly as in the reference
+# (none of the driver names is a substring of it).
 preprocess_bc = ("impulse")
 postprocess_bc = ("fixed_cube", "sticky_ground")
 init_bc = ("additional_params", "modify_material")
 collider_bc = ("collider",)  # extended colliders: grid_postprocess entries with a window of their own
+# particle drivers: particle_preprocess entries on a fixed selection, applied after the impulses
+driver_bc = ("particle_impulse", "enforce_particle_translation", "enforce_particle_rotation")
 
 boundaryConditionTypeCallBacks = {
     "fixed_cube": BasicBC,
@@ -217,4 +277,7 @@ boundaryConditionTypeCallBacks = {
     "additional_params": MaterialParamsModifier,
     "modify_material": MaterialTypeModifier,
     "collider": ColliderBC,
+    "particle_impulse": ParticleDriverBC,
+    "enforce_particle_translation": ParticleDriverBC,
+    "enforce_particle_rotation": ParticleDriverBC,
 }

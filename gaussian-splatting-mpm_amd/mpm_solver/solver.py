@@ -18,8 +18,9 @@ import math
 
 from gsmpm.fit import FitSimulator
 from gsmpm.sim import Simulator
-from mpm_solver.boundary_conditions import (ColliderBC, StickyGroundBC, boundaryConditionTypeCallBacks, collider_bc,
-                                            init_bc, postprocess_bc, preprocess_bc)
+from mpm_solver.boundary_conditions import (ColliderBC, ParticleDriverBC, StickyGroundBC,
+                                            boundaryConditionTypeCallBacks, collider_bc, driver_bc, init_bc,
+                                            postprocess_bc, preprocess_bc)
 from mpm_solver.collider import MPM_Collider, collideTypeCallBacks
 from mpm_solver.model import MPM_model, MPM_state, MPM_state_opt
 
@@ -123,6 +124,9 @@ class MPM_Simulator:
                 if bc_args["type"] in collider_bc:
                     raise TypeError("collider records apply to the forward-only simulator; the fitting path "
                                     "(MPM_state_opt) has no extended colliders")
+                if bc_args["type"] in driver_bc:
+                    raise TypeError("particle driver records apply to the forward-only simulator; the fitting path "
+                                    "(MPM_state_opt) has no particle drivers")
                 bc = boundaryConditionTypeCallBacks[bc_args["type"]](self.n_particles, bc_args, sim_args)
                 if bc.type in postprocess_bc:
                     self.grid_postprocess.append(bc)
@@ -140,6 +144,8 @@ class MPM_Simulator:
                 self.grid_postprocess.append(bc)
             if bc.type in collider_bc:
                 self._add_collider_bc(bc)
+            if bc.type in driver_bc:
+                self._add_driver_bc(bc)
             if bc.type in init_bc:
                 self.init_particles.append(bc)
         # solver.py:125-129, in list order (a later box overrides an earlier one).  An
@@ -196,6 +202,53 @@ class MPM_Simulator:
         self.flush()  # substeps queued so far ran without it
         bc.bit = self._sim.add_collider(bc.shape, bc.surface, bc.friction, bc.damping, **bc.geometry, **bc.motion)
         self.grid_postprocess.append(bc)
+
+    # ---------------------------------------------------- particle drivers --
+    # Records on a selection of particles chosen at the call (the rows inside
+    # center / size now, or the rows of mask) and fixed from then on
+    # (gsmpm_mpm_add_driver); each returns its descriptor (``bit``: the
+    # library's bc id) and is the same record as a set_boundary_conditions
+    # entry of that type.  Within a substep they run after every box impulse,
+    # in the order they were added, before the stress.
+    def add_particle_impulse(self, force, *, center=None, size=None, mask=None, start_time=0.0, end_time=None,
+                             num_dt=None, substep_dt=None):
+        """v += force / m * substep_dt on the selection (ImpulseBC's arithmetic;
+        substep_dt is needed here, there being no sim_args)."""
+        if substep_dt is None:
+            raise TypeError("add_particle_impulse: substep_dt is required")
+        return self._new_driver("particle_impulse", dict(force=force, substep_dt=substep_dt), center, size, mask,
+                                start_time, end_time, num_dt, substep_dt)
+
+    def enforce_particle_translation(self, velocity, *, center=None, size=None, mask=None, start_time=0.0,
+                                     end_time=None, num_dt=None, substep_dt=None):
+        """v = velocity on the selection (num_dt needs substep_dt)."""
+        return self._new_driver("enforce_particle_translation", dict(velocity=velocity), center, size, mask,
+                                start_time, end_time, num_dt, substep_dt)
+
+    def enforce_particle_rotation(self, point, axis, omega=0.0, along=0.0, *, center=None, size=None, mask=None,
+                                  start_time=0.0, end_time=None, num_dt=None, substep_dt=None):
+        """v = omega * cross(axis, x - point) + along * axis on the selection
+        (the axis is normalised; num_dt needs substep_dt)."""
+        return self._new_driver("enforce_particle_rotation", dict(point=point, axis=axis, omega=omega, along=along),
+                                center, size, mask, start_time, end_time, num_dt, substep_dt)
+
+    def _new_driver(self, kind, params, center, size, mask, start_time, end_time, num_dt, substep_dt):
+        if self.fitting:
+            raise TypeError("particle drivers apply to the forward-only simulator; the fitting path (MPM_state_opt) "
+                            "has no particle drivers")
+        if num_dt is not None and substep_dt is None:
+            raise TypeError(f"{kind}: num_dt needs substep_dt")
+        from types import SimpleNamespace
+        bc = ParticleDriverBC(self.n_particles, dict(params, type=kind, center=center, size=size, mask=mask,
+                                                     start_time=start_time, end_time=end_time, num_dt=num_dt),
+                              SimpleNamespace(substep_dt=substep_dt))
+        self._add_driver_bc(bc)
+        return bc
+
+    def _add_driver_bc(self, bc):
+        self.flush()  # substeps queued so far ran without it, and a box selects the positions they lead to
+        bc.bit = self._sim.add_driver(bc.type, center=bc.center, size=bc.size, mask=bc.mask, **bc.params)
+        self.particle_preprocess.append(bc)
 
     # ------------------------------------------- differentiable (fitting) --
     def _need_fit(self, name):

@@ -255,6 +255,59 @@ typedef struct {
 } gsmpm_collider_spin;
 int gsmpm_mpm_add_rotating_collider(gsmpm_mpm* h, const gsmpm_collider* collider,
                                     const gsmpm_collider_spin* spin);
+/* Particle drivers: a boundary-condition record attached to a fixed SELECTION
+ * of particles -- ImpulseBC with the mask its "#TODO: Need to replace this
+ * with a mask" (boundary_conditions.py:43) asks for, and two records that
+ * enforce a velocity on the selection.  The selection is chosen once, when
+ * the record is added, and is held per caller row: a re-bin, a re-sort, a
+ * permuted input or gsmpm_mpm_set_particles never changes who is selected,
+ * and a particle that leaves the box it was chosen with stays driven.
+ * With x, v, m the particle's values in the front of P2G (registers only:
+ * G2P replaces particle_v afterwards), all arithmetic f32, unfused:
+ *   PARTICLE_IMPULSE    v += force / m * substep_dt        (ImpulseBC.apply's arithmetic)
+ *   ENFORCE_TRANSLATION v  = velocity                      (the f32 of the doubles given)
+ *   ENFORCE_ROTATION    v  = omega * cross(axis, x - point) + along * axis
+ *                       (axis normalised in f64 here and rounded once; the
+ *                       axis line is invariant under the motion, so no clock)
+ * Order inside a substep: the box impulses (gsmpm_mpm_add_impulse) in their
+ * order, then the drivers in the order they were added, then the stress --
+ * particle_preprocess (solver.py:41-42) with the drivers after the impulses;
+ * a later enforce overrides an earlier kick and a later kick adds to an
+ * earlier enforce.  The driven v enters the non-finite check and the P2G
+ * scatter as a kicked v does.  The record takes one bc id and honours its
+ * bit of bc_active (NULL: active); the caller's clock decides its window.
+ * Selection: with mask == NULL the rows whose current position passes the
+ * region records' strict f32 test |x - center| < size on every axis (a
+ * kernel on `stream`); else mask[n] bytes on the device, caller order, non-zero
+ * = selected (center / size ignored).  An empty selection is legal.  The
+ * first driver allocates one uint32 word per particle (4 * capacity bytes,
+ * once; bit j = the j-th driver) and switches the handle to the driver entry
+ * points of its P2G kernels (k_fused_drv, k_p2g_drv and their mixed forms);
+ * a handle without one launches the kernels it always did.
+ * Returns the bc id, or GSMPM_EINVAL: unknown kind, a non-finite parameter,
+ * a zero axis, a box size <= 0 (or a non-finite box) without a mask, too
+ * many BCs.  GSMPM_ESTATE, with a message and nothing changed: a slab handle
+ * (migration moves rows between ranks; gsmpm_mpm_slab_init refuses a handle
+ * that holds a driver), a handle created with GSMPM_FOLD=1, particles not
+ * set.  The differentiable simulator (gsmpm_fit_*) has no drivers. */
+#define GSMPM_DRIVER_PARTICLE_IMPULSE 0
+#define GSMPM_DRIVER_ENFORCE_TRANSLATION 1
+#define GSMPM_DRIVER_ENFORCE_ROTATION 2
+typedef struct {
+  int32_t kind;                /* GSMPM_DRIVER_* */
+  double center[3], size[3];   /* selection box (mask == NULL) */
+  double force[3];             /* PARTICLE_IMPULSE */
+  double substep_dt;           /* PARTICLE_IMPULSE */
+  double velocity[3];          /* ENFORCE_TRANSLATION */
+  double point[3], axis[3];    /* ENFORCE_ROTATION: a point of the axis, its direction (any length > 0) */
+  double omega, along;         /* ENFORCE_ROTATION: angular speed about the axis, speed along it */
+} gsmpm_driver;
+int gsmpm_mpm_add_driver(gsmpm_mpm* h, const gsmpm_driver* driver, const uint8_t* mask_or_null /* device [n] */,
+                         void* stream);
+/* The selection of the driver with bc id `id`, out[n] bytes (0 / 1) on the
+ * device, caller order.  GSMPM_EINVAL: no driver has that id. */
+int gsmpm_mpm_get_driver_selection(gsmpm_mpm* h, int32_t id, uint8_t* out /* device [n] */, void* stream);
+
 /* Diagnostics: synchronizes `stream` and copies the poses of the last step
  * call, out[n_substeps][n_rot][16], rotating records in table order.
  * GSMPM_ESTATE on a handle without rotating records, GSMPM_EINVAL for more
