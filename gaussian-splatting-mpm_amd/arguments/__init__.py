@@ -14,7 +14,9 @@ take an optional "yield_stress": configs/lego-melt.json), ModelParams.synthetic 
 Gaussians when the scene's PLY is absent / an LFS pointer),
 RenderParams.rotate_sh (SH view directions follow particle_R),
 RenderParams.save_pcd_deformed (--save_pcd writes the deformed Gaussians as a
-standard 3DGS PLY: scales, rotations, rotated SH, filled particles), and the optional top-level ``particle_filling`` record (FillingParams: JSON
+standard 3DGS PLY: scales, rotations, rotated SH, filled particles),
+RenderParams.save_alpha / save_depth (RGBA frames and depth/%04d.npy from the
+rasterizer's alpha and depth maps: configs/lego-matte.json), and the optional top-level ``particle_filling`` record (FillingParams: JSON
 only, no flags; absent = no filling).
 """
 from argparse import ArgumentParser
@@ -100,6 +102,8 @@ class RenderParams(ParamGroup):
         self.save_pcd_interval = 10
         self.rotate_sh = False  # shade each Gaussian at particle_R d (PhysGaussian's f_0(R^T d))
         self.save_pcd_deformed = False  # --save_pcd writes scales / rotations / SH of the deformed state too
+        self.save_alpha = False  # frames as RGBA PNGs, A = the rasterizer's alpha map rounded to 8 bits
+        self.save_depth = False  # depth/%04d.npy: the rasterizer's depth map over its alpha map
         super().__init__(parser, "Render Parameters", json_params)
 
 

@@ -45,6 +45,12 @@
 // physical Q is particle_R, which the project stores as (U V^T)^T = R^T
 // (utils.py:376-398), so Q d = R^T d: PhysGaussian's f_t(d) = f_0(R^T d).
 // ROT = false is the code that ran before the option existed.
+//
+// aux_depth / aux_alpha (gsmpm_raster_args, opt-in; forward only, no gradient):
+// k_render<AUX> / k_render4<AUX> also fold D = sum z_i alpha_i T_i over the
+// contributors the colour blend takes (z_i: the view depth k_preprocess
+// stored) and write D and A = 1 - T_final.  AUX = false is the code that ran
+// before the option existed.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/block/block_radix_sort.hpp>
@@ -524,16 +530,25 @@ __device__ __forceinline__ bool render_quarter(int xcd, int gx, int ntiles, int 
   by = 2 * (tile / gx) + (h >> 1);
   return true;
 }
+// AUX: the depth and alpha maps (gsmpm_raster_args.aux_depth / aux_alpha).  An
+// entry's view depth zsrc[id] is gathered with its xy / conic / rgb (same
+// relevance test, same place in the issue order), staged in s_z and folded as
+// D = fma(z, alpha T, D) beside the colours; D and 1 - T are stored for inside
+// pixels (either pointer may be null).  The colour arithmetic is untouched, so
+// pixels, final T and last contributor are those of AUX = false.
+template <bool AUX>
 __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges, const unsigned* __restrict__ list,
                                                int W, int H, int gx, const float2* __restrict__ xy,
                                                const float4* __restrict__ conic_o, const float4* __restrict__ rgbo,
                                                const float* __restrict__ bg, float* __restrict__ out,
                                                float* __restrict__ final_T, int* __restrict__ n_contrib,
                                                const unsigned* __restrict__ tkeys, int mode, int xcd, int ntiles,
-                                               int nq) {
+                                               int nq, const float* __restrict__ zsrc, float* __restrict__ aux_depth,
+                                               float* __restrict__ aux_alpha) {
   __shared__ float2 s_xy[kBatchR];
   __shared__ float4 s_co[kBatchR];
   __shared__ float4 s_rgb[kBatchR];  // .w: the entry's tile-list index (as int bits)
+  __shared__ float s_z[AUX ? kBatchR : 1];  // AUX: the entry's view depth
   // one quarter per workgroup, or (a grid of fewer workgroups, a multiple of 8
   // so a quarter keeps its XCD) quarters L, L + grid, ...
   for (int L = blockIdx.x; L < nq; L += gridDim.x) {
@@ -548,6 +563,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
   const unsigned* lst = list + range.x;
   const float pfx = (float)px, pfy = (float)py, fx0 = (float)x0, fy0 = (float)y0;
   float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+  [[maybe_unused]] float D = 0.f;
   int last = 0;
   bool done = !inside;
   // lane holds entries j0 + 64 q + lane, q < kQR
@@ -563,6 +579,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
   // wave for kQR round trips in front of every blend.
   float2 g_xy[kQR];
   float4 g_co[kQR], g_rgb[kQR];
+  [[maybe_unused]] float g_z[kQR];
   unsigned gid[kQR], gkey[kQR], nid[kQR], nkey[kQR];
   bool g_rel[kQR];
 #pragma unroll
@@ -577,11 +594,13 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
   for (int q = 0; q < kQR; ++q) {
     g_xy[q] = make_float2(0.f, 0.f);
     g_co[q] = g_rgb[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (AUX) g_z[q] = 0.f;
     g_rel[q] = 64 * q + lane < n && (gkey[q] & qbit);
     if (g_rel[q]) {
       g_xy[q] = xy[gid[q]];
       g_co[q] = conic_o[gid[q]];
       g_rgb[q] = rgbo[gid[q]];
+      if constexpr (AUX) g_z[q] = zsrc[gid[q]];
     }
   }
   for (int j0 = 0; j0 < n; j0 += kBatchR) {
@@ -600,6 +619,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
         s_xy[pos] = g_xy[q];
         s_co[pos] = g_co[q];
         s_rgb[pos] = make_float4(g_rgb[q].x, g_rgb[q].y, g_rgb[q].z, __int_as_float(j));
+        if constexpr (AUX) s_z[pos] = g_z[q];
       }
       cnt += __popcll(m);
     }
@@ -607,6 +627,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
       s_xy[cnt + lane] = make_float2(0.f, 0.f);
       s_co[cnt + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
       s_rgb[cnt + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (AUX) s_z[cnt + lane] = 0.f;
     }
     __syncthreads();
     // the next batch's gather and the one after's list ids fly while this one blends
@@ -615,12 +636,14 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
     // the in-order counter turns into a wait for the gather just issued)
     const float2* pxy[kQR];
     const float4 *pco[kQR], *prgb[kQR];
+    [[maybe_unused]] const float* pz[kQR];
 #pragma unroll
     for (int q = 0; q < kQR; ++q) {
       g_rel[q] = j0 + kBatchR + 64 * q + lane < n && (nkey[q] & qbit);
       pxy[q] = xy + nid[q];
       pco[q] = conic_o + nid[q];
       prgb[q] = rgbo + nid[q];
+      if constexpr (AUX) pz[q] = zsrc + nid[q];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -629,6 +652,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
         g_xy[q] = *pxy[q];
         g_co[q] = *pco[q];
         g_rgb[q] = *prgb[q];
+        if constexpr (AUX) g_z[q] = *pz[q];
       }
     }
 #pragma unroll
@@ -641,11 +665,13 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
       if (__all(done)) break;
       float al[kU];
       float4 c[kU];
+      [[maybe_unused]] float z[kU];
 #pragma unroll
       for (int k = 0; k < kU; ++k) {
         const float2 g = s_xy[b + k];
         const float4 co = s_co[b + k];
         c[k] = s_rgb[b + k];
+        if constexpr (AUX) z[k] = s_z[b + k];
         const float dx = g.x - pfx, dy = g.y - pfy;
         // the hardware exp2 (v_exp_f32, ~1 ulp): pixel parity is 1e-3, not bitwise
         const float power = __builtin_fmaf(-0.5f, __builtin_fmaf(co.x * dx, dx, co.z * dy * dy), -co.y * dx * dy);
@@ -664,6 +690,7 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
         C0 = __builtin_fmaf(c[k].x, aT, C0);
         C1 = __builtin_fmaf(c[k].y, aT, C1);
         C2 = __builtin_fmaf(c[k].z, aT, C2);
+        if constexpr (AUX) D = __builtin_fmaf(z[k], aT, D);
         T = take ? test_T : T;
         last = take ? __float_as_int(c[k].w) + 1 : last;
       }
@@ -678,6 +705,10 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
     if (final_T) {  // the backward's per-pixel state; a forward-only context skips it
       final_T[pix] = T;
       n_contrib[pix] = last;
+    }
+    if constexpr (AUX) {
+      if (aux_depth) aux_depth[pix] = D;
+      if (aux_alpha) aux_alpha[pix] = 1.0f - T;
     }
   }
   }
@@ -694,16 +725,21 @@ __global__ __launch_bounds__(64) void k_render(const uint2* __restrict__ ranges,
 // and last contributor).  Staging is double-buffered: one barrier a batch,
 // and the next batch's gathers are in flight while this one blends.  The
 // workgroup stops when all 256 pixels are done.
+// AUX: as k_render<AUX> (the depth staged in s_z beside the other arrays).
 constexpr int kStage = kBatch + kU;  // + kU all-zero slots: the padding of a wave's last group of kU
+template <bool AUX>
 __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ ranges, const unsigned* __restrict__ list,
                                                  int W, int H, int gx, const float2* __restrict__ xy,
                                                  const float4* __restrict__ conic_o, const float4* __restrict__ rgbo,
                                                  const float* __restrict__ bg, float* __restrict__ out,
                                                  float* __restrict__ final_T, int* __restrict__ n_contrib,
-                                                 const unsigned* __restrict__ tkeys, int mode) {
+                                                 const unsigned* __restrict__ tkeys, int mode,
+                                                 const float* __restrict__ zsrc, float* __restrict__ aux_depth,
+                                                 float* __restrict__ aux_alpha) {
   __shared__ float2 s_xy[2][kStage];
   __shared__ float4 s_co[2][kStage];
   __shared__ float4 s_rgb[2][kStage];  // .w: the entry's tile-list index (as int bits)
+  __shared__ float s_z[2][AUX ? kStage : 1];  // AUX: the entry's view depth
   __shared__ unsigned char s_m[2][kBatch];
   __shared__ unsigned short s_idx[4][kBatch + kU];
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
@@ -716,6 +752,7 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
   const unsigned* tk = tkeys ? tkeys + range.x : nullptr;
   const float pfx = (float)px, pfy = (float)py, fx0 = (float)x0, fy0 = (float)y0;
   float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+  [[maybe_unused]] float D = 0.f;
   int last = 0;
   bool done = !inside;
   if (t < kU)
@@ -723,10 +760,12 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
       s_xy[b][kBatch + t] = make_float2(0.f, 0.f);
       s_co[b][kBatch + t] = make_float4(0.f, 0.f, 0.f, 0.f);
       s_rgb[b][kBatch + t] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (AUX) s_z[b][kBatch + t] = 0.f;
     }
   // lane t's entry of the current batch (gathered) and of the next (id, mask)
   float2 g_xy = make_float2(0.f, 0.f);
   float4 g_co = make_float4(0.f, 0.f, 0.f, 0.f), g_rgb = g_co;
+  [[maybe_unused]] float g_z = 0.f;
   unsigned g_m = 0, n_id = 0, n_m = 0;
   auto mask_of = [&](int j) -> unsigned { return tk ? (tk[j] >> kMaskShift) & 0xfu : 0xfu; };
   if (t < n) {
@@ -736,6 +775,7 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
       g_xy = xy[id];
       g_co = conic_o[id];
       g_rgb = rgbo[id];
+      if constexpr (AUX) g_z = zsrc[id];
     }
   }
   if (kBatch + t < n) {
@@ -747,6 +787,7 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
     s_xy[buf][t] = g_xy;
     s_co[buf][t] = g_co;
     s_rgb[buf][t] = make_float4(g_rgb.x, g_rgb.y, g_rgb.z, __int_as_float(j0 + t));
+    if constexpr (AUX) s_z[buf][t] = g_z;
     s_m[buf][t] = (unsigned char)(j0 + t < n ? g_m : 0u);
     if (__syncthreads_count(!done) == 0) break;
     // the next batch's gather and the one after's ids fly while this one blends
@@ -755,6 +796,7 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
       g_xy = xy[n_id];
       g_co = conic_o[n_id];
       g_rgb = rgbo[n_id];
+      if constexpr (AUX) g_z = zsrc[n_id];
     }
     if (j0 + 2 * kBatch + t < n) {
       n_id = lst[j0 + 2 * kBatch + t];
@@ -784,12 +826,14 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
       if (__all(done)) break;
       float al[kU];
       float4 c[kU];
+      [[maybe_unused]] float z[kU];
 #pragma unroll
       for (int k = 0; k < kU; ++k) {
         const int e = s_idx[q][b + k];
         const float2 g = s_xy[buf][e];
         const float4 co = s_co[buf][e];
         c[k] = s_rgb[buf][e];
+        if constexpr (AUX) z[k] = s_z[buf][e];
         const float dx = g.x - pfx, dy = g.y - pfy;
         const float power = __builtin_fmaf(-0.5f, __builtin_fmaf(co.x * dx, dx, co.z * dy * dy), -co.y * dx * dy);
         const float alpha = fminf(0.99f, co.w * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
@@ -806,6 +850,7 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
         C0 = __builtin_fmaf(c[k].x, aT, C0);
         C1 = __builtin_fmaf(c[k].y, aT, C1);
         C2 = __builtin_fmaf(c[k].z, aT, C2);
+        if constexpr (AUX) D = __builtin_fmaf(z[k], aT, D);
         T = take ? test_T : T;
         last = take ? __float_as_int(c[k].w) + 1 : last;
       }
@@ -819,6 +864,10 @@ __global__ __launch_bounds__(256) void k_render4(const uint2* __restrict__ range
     if (final_T) {
       final_T[pix] = T;
       n_contrib[pix] = last;
+    }
+    if constexpr (AUX) {
+      if (aux_depth) aux_depth[pix] = D;
+      if (aux_alpha) aux_alpha[pix] = 1.0f - T;
     }
   }
 }
@@ -2747,15 +2796,21 @@ int gsmpm_raster_forward(gsmpm_raster* r, const gsmpm_raster_args* in, float* ou
   // (A/B: a render overlapping the simulator holds fewer of the CU slots its one-round launches need)
   if (const char* rw = std::getenv("GSMPM_RASTER_RENDER_WGS"))
     if (xcd && std::atoi(rw) >= 8) rgrid = dim3((unsigned)std::min(nq, std::atoi(rw) & ~7));
+  // aux_depth / aux_alpha select the AUX instantiation; without them the kernel is the one it always was.
+  // r->depth (k_preprocess's view depths) has a buffer of its own on every path and nothing after
+  // k_preprocess writes it: the depth orders and k_duplicate only read it
+  const bool aux = in->aux_depth || in->aux_alpha;
   tmg.mark(1);
   if (!(ts && ts[0] == '1'))
-    hipLaunchKernelGGL(k_render, rgrid, dim3(64), 0, st, r->ranges, r->ids_sorted, a.W, a.H, a.grid_x, r->xy, r->conic,
-                       r->rgb, in->bg, out_color, r->forward_only ? nullptr : r->final_T,
-                       r->forward_only ? nullptr : r->n_contrib, tkeys, render_mode, xcd, (int)ntiles, nq);
+    hipLaunchKernelGGL(aux ? k_render<true> : k_render<false>, rgrid, dim3(64), 0, st, r->ranges, r->ids_sorted, a.W,
+                       a.H, a.grid_x, r->xy, r->conic, r->rgb, in->bg, out_color,
+                       r->forward_only ? nullptr : r->final_T, r->forward_only ? nullptr : r->n_contrib, tkeys,
+                       render_mode, xcd, (int)ntiles, nq, (const float*)r->depth, in->aux_depth, in->aux_alpha);
   else
-    hipLaunchKernelGGL(k_render4, dim3(a.grid_x, a.grid_y), dim3(256), 0, st, r->ranges, r->ids_sorted, a.W, a.H,
-                       a.grid_x, r->xy, r->conic, r->rgb, in->bg, out_color, r->forward_only ? nullptr : r->final_T,
-                       r->forward_only ? nullptr : r->n_contrib, tkeys, render_mode);
+    hipLaunchKernelGGL(aux ? k_render4<true> : k_render4<false>, dim3(a.grid_x, a.grid_y), dim3(256), 0, st, r->ranges,
+                       r->ids_sorted, a.W, a.H, a.grid_x, r->xy, r->conic, r->rgb, in->bg, out_color,
+                       r->forward_only ? nullptr : r->final_T, r->forward_only ? nullptr : r->n_contrib, tkeys,
+                       render_mode, (const float*)r->depth, in->aux_depth, in->aux_alpha);
   tmg.mark(2);
   r->has_pixel_state = !r->forward_only;
   GSMPM_LAUNCH_CHECK();
@@ -2957,6 +3012,10 @@ int gsmpm_raster_forward_async(const gsmpm_raster_args* a, float* out_color, int
     hipLaunchKernelGGL(k_fill_bg, dim3(div_up((long)a->W * a->H, 256)), dim3(256), 0, st, a->bg, a->W * a->H,
                        out_color, counts);
     GSMPM_LAUNCH_CHECK();
+    // nothing reaches any pixel: D = 0, A = 0
+    const size_t map_bytes = (size_t)a->W * a->H * sizeof(float);
+    if (a->aux_depth) GSMPM_HIP(hipMemsetAsync(a->aux_depth, 0, map_bytes, st));
+    if (a->aux_alpha) GSMPM_HIP(hipMemsetAsync(a->aux_alpha, 0, map_bytes, st));
     return GSMPM_OK;
   }
   WsCount* c = nullptr;

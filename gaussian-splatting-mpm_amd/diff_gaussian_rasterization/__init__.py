@@ -8,9 +8,12 @@ _RasterizeGaussians.backward, used by extra.py's loss.backward()) returns the
 gradients of means3D, means2D (w.r.t. NDC, as upstream), shs / colors_precomp,
 opacities, scales / rotations or cov3D_precomp; a forward that needs them runs
 on a context of its own (leased from a per-device pool) that keeps its
-binning and per-pixel state until the backward.  One addition, last and
-optional everywhere: ``sh_rotations`` ([P,3,3] or [P,9]) shades each Gaussian
-at Q d instead of the view direction d, and gets its gradient too.
+binning and per-pixel state until the backward.  Two additions, last,
+optional and passed by keyword everywhere: ``sh_rotations`` ([P,3,3] or [P,9]) shades each Gaussian
+at Q d instead of the view direction d, and gets its gradient too;
+``return_depth_alpha=True`` makes the forward return ``(color, radii, depth,
+alpha)``, depth [H,W] = sum z_i alpha_i T_i (view-space depth, not normalised)
+and alpha [H,W] = 1 - T_final of the colour blend, both non-differentiable.
 """
 from __future__ import annotations
 
@@ -38,11 +41,15 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, sh_rotations=None):
-    """Upstream's positional signature; sh_rotations ([P,3,3] or [P,9], not in
-    upstream) evaluates each Gaussian's SH at Q d instead of the view direction d."""
+                        raster_settings, return_depth_alpha=False, sh_rotations=None):
+    """Upstream's positional signature, then the two additions, both passed by
+    keyword: return_depth_alpha appends the depth and alpha maps to (color,
+    radii); sh_rotations ([P,3,3] or [P,9]) evaluates each Gaussian's SH at Q d
+    instead of the view direction d."""
+    if isinstance(return_depth_alpha, torch.Tensor):
+        raise TypeError("rasterize_gaussians: pass sh_rotations by keyword (return_depth_alpha precedes it)")
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, sh_rotations)
+                                     cov3Ds_precomp, raster_settings, sh_rotations, bool(return_depth_alpha))
 
 
 def _opt(t):
@@ -52,29 +59,29 @@ def _opt(t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, sh_rotations=None):
+                raster_settings, sh_rotations=None, return_depth_alpha=False):
         s = raster_settings
-        kw = dict(sh_degree=s.sh_degree, shs=_opt(sh), colors_precomp=_opt(colors_precomp), scales=_opt(scales),
+        kw = dict(depth=return_depth_alpha, alpha=return_depth_alpha, sh_degree=s.sh_degree, shs=_opt(sh), colors_precomp=_opt(colors_precomp), scales=_opt(scales),
                   rotations=_opt(rotations), cov3D_precomp=_opt(cov3Ds_precomp), scale_modifier=s.scale_modifier,
                   prefiltered=s.prefiltered, sh_rotations=_opt(sh_rotations))
         args = (means3D, opacities.reshape(-1), s.viewmatrix, s.projmatrix, s.campos, s.bg, s.image_height,
                 s.image_width, s.tanfovx, s.tanfovy)
         if any(ctx.needs_input_grad[:8]) or ctx.needs_input_grad[9]:
             lease = _raster.ContextLease(means3D.device.index or 0)
-            num_rendered, color, radii, a, keep = _raster.forward(*args, **kw, context=lease.context,
-                                                                  return_args=True)
+            num_rendered, color, radii, *maps, a, keep = _raster.forward(*args, **kw, context=lease.context,
+                                                                         return_args=True)
             ctx.state = (lease, a, keep, radii)
             ctx.shapes = [None if t is None else (t.shape, t.dtype) for t in
                           (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                            None, sh_rotations)]
         else:
-            num_rendered, color, radii = _raster.forward(*args, **kw)
+            num_rendered, color, radii, *maps = _raster.forward(*args, **kw)
         ctx.num_rendered = num_rendered
-        ctx.mark_non_differentiable(radii)
-        return color, radii
+        ctx.mark_non_differentiable(radii, *maps)
+        return (color, radii, *maps)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _):
+    def backward(ctx, grad_out_color, *_):
         lease, a, keep, radii = ctx.state
         shp = ctx.shapes
         P = a.P
@@ -84,13 +91,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 return None
             return t.reshape(shp[i][0]).to(shp[i][1])
         if P == 0:
-            return (None,) * 10
+            return (None,) * 11
         g = _raster.backward(lease.context, keep, a, radii, grad_out_color)
         lease.release()  # back to the pool: the next iteration's forward reuses its buffers
         ctx.state = None
         return (cast(g["means3D"], 0), cast(g["means2D"], 1), cast(g["sh"], 2), cast(g["colors"], 3),
                 cast(g["opacity"], 4), cast(g["scales"], 5), cast(g["rotations"], 6), cast(g["cov3D"], 7), None,
-                cast(g["sh_rotations"], 9))
+                cast(g["sh_rotations"], 9), None)
 
 
 class GaussianRasterizer(nn.Module):
@@ -104,7 +111,7 @@ class GaussianRasterizer(nn.Module):
             return _raster.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, sh_rotations=None):
+                cov3D_precomp=None, return_depth_alpha=False, sh_rotations=None):
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -115,4 +122,5 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, empty if shs is None else shs,
                                    empty if colors_precomp is None else colors_precomp, opacities,
                                    empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, s, sh_rotations)
+                                   empty if cov3D_precomp is None else cov3D_precomp, s,
+                                   return_depth_alpha=return_depth_alpha, sh_rotations=sh_rotations)

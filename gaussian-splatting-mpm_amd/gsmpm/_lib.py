@@ -78,6 +78,7 @@ class RasterArgs(ctypes.Structure):
         ("tanfovx", ctypes.c_float), ("tanfovy", ctypes.c_float),
         ("prefiltered", ctypes.c_int32),
         ("sh_rotations", c_void_p),
+        ("aux_depth", c_void_p), ("aux_alpha", c_void_p),
     ]
 
 

@@ -250,13 +250,19 @@ def backward(context, keep, a, radii, grad_color):
 
 def forward(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
             sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
-            scale_modifier=1.0, prefiltered=False, context=None, return_args=False, ws=None, sh_rotations=None):
-    """Returns (num_rendered, color [3,H,W], radii [P] int32) [+ (args, kept tensors)
-    when return_args].  `context` (a RasterContext, or a SharedContext) keeps
-    this forward's state (for `backward`, or the diagnostics); by default the
-    forward runs in the device's caller-owned Workspace (or `ws`).
+            scale_modifier=1.0, prefiltered=False, context=None, return_args=False, ws=None, depth=False, alpha=False,
+            sh_rotations=None):
+    """Returns (num_rendered, color [3,H,W], radii [P] int32) [+ depth [H,W] when
+    `depth`] [+ alpha [H,W] when `alpha`] [+ (args, kept tensors) when
+    return_args], in that order.  `context` (a RasterContext, or a
+    SharedContext) keeps this forward's state (for `backward`, or the
+    diagnostics); by default the forward runs in the device's caller-owned
+    Workspace (or `ws`).
     sh_rotations [P,3,3] | [P,9]: evaluate each Gaussian's SH at Q d instead of
-    the view direction d (include/gsmpm.h, gsmpm_raster_args.sh_rotations)."""
+    the view direction d (include/gsmpm.h, gsmpm_raster_args.sh_rotations).
+    depth / alpha: new f32 tensors holding D = sum z_i alpha_i T_i (view-space
+    depth, not normalised) and A = 1 - T_final of the colour blend
+    (gsmpm_raster_args.aux_depth / aux_alpha); no gradient flows to them."""
     dev = means3D.device
     a, keep = _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx,
                     tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier,
@@ -264,10 +270,17 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height
     P = a.P
     color = torch.empty((3, image_height, image_width), dtype=torch.float32, device=dev)
     radii = torch.empty(P, dtype=torch.int32, device=dev)  # k_preprocess writes every entry (0 when culled)
+    # the kernel writes every pixel of a requested map
+    maps = [torch.empty((image_height, image_width), dtype=torch.float32, device=dev) if on else None
+            for on in (depth, alpha)]
+    a.aux_depth, a.aux_alpha = ptr(maps[0]), ptr(maps[1])
     nr = ctypes.c_int32(0)
     if P == 0:
-        # nothing to splat: the image is the background (upstream behaviour)
+        # nothing to splat: the image is the background (upstream behaviour), the maps are zero
         color[:] = keep["bg"].view(3, 1, 1)
+        for m in maps:
+            if m is not None:
+                m.zero_()
     elif context is not None:
         with torch.cuda.device(dev):
             check(LIB.gsmpm_raster_forward(context.h, ctypes.byref(a), ptr(color), ptr(radii), ctypes.byref(nr),
@@ -285,9 +298,10 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height
                     break
                 w.ensure(P, H, W, int(need.value) + int(need.value) // 4 + 1024)
             check(rc, "rasterize_gaussians")
+    out = (int(nr.value), color, radii) + tuple(m for m in maps if m is not None)
     if return_args:
-        return int(nr.value), color, radii, a, keep
-    return int(nr.value), color, radii
+        out += (a, keep)
+    return out
 
 
 class AsyncRender:
@@ -295,8 +309,9 @@ class AsyncRender:
     its counts {K, num_rendered, flags, internal} in pinned host memory, valid
     once the stream has passed the render (done())."""
 
-    def __init__(self, color, radii, counts, event, args):
+    def __init__(self, color, radii, counts, event, args, depth=None, alpha=None):
         self.color, self.radii, self.counts, self.event, self._args = color, radii, counts, event, args
+        self.depth, self.alpha = depth, alpha  # the caller's map tensors (forward_async's depth / alpha), or None
 
     def done(self) -> bool:
         return self.event is None or self.event.query()
@@ -316,17 +331,24 @@ class AsyncRender:
 def forward_async(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx, tanfovy,
                   sh_degree=0, shs=None, colors_precomp=None, cov3D_precomp=None, scales=None, rotations=None,
                   scale_modifier=1.0, pairs_cap=None, ws=None, counts=None, color=None, radii=None,
-                  sh_rotations=None):
+                  depth=None, alpha=None, sh_rotations=None):
     """gsmpm_raster_forward_async: the forward with no host synchronisation
     (the pair count stays on the device; buffers carved for pairs_cap pairs,
     default the workspace's).  Returns an AsyncRender; a frame whose flags
     are set (a depth bucket overflow, or more pairs than pairs_cap) must be
-    rendered again by forward()."""
+    rendered again by forward().  depth / alpha: caller-owned contiguous f32
+    [H,W] tensors the render fills (gsmpm_raster_args.aux_depth / aux_alpha;
+    the AsyncRender carries them), as `color` and `radii` may be."""
     dev = means3D.device
     a, keep = _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx,
                     tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, False,
                     sh_rotations)
     H, W = int(image_height), int(image_width)
+    for name, m in (("depth", depth), ("alpha", alpha)):
+        if m is not None and not (m.dtype == torch.float32 and m.is_contiguous() and tuple(m.shape) == (H, W)
+                                  and m.device == dev):
+            raise ValueError(f"forward_async: {name} must be a contiguous float32 [{H},{W}] tensor on {dev}")
+    a.aux_depth, a.aux_alpha = ptr(depth), ptr(alpha)
     color = torch.empty((3, H, W), dtype=torch.float32, device=dev) if color is None else color
     radii = torch.empty(a.P, dtype=torch.int32, device=dev) if radii is None else radii
     counts = torch.zeros(4, dtype=torch.int32, pin_memory=True) if counts is None else counts
@@ -341,7 +363,7 @@ def forward_async(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_
         if not torch.cuda.is_current_stream_capturing():  # a graph replay is waited on by its caller
             ev = torch.cuda.Event()
             ev.record()
-    return AsyncRender(color, radii, counts, ev, (a, keep))
+    return AsyncRender(color, radii, counts, ev, (a, keep), depth, alpha)
 
 
 def set_timing(on):

@@ -2,6 +2,7 @@
 
     python main.py --config_path configs/lego.json [--n_grid 128] [--synthetic 100000]
                    [--output_path out/lego] [--white_background] [--save_pcd [--save_pcd_deformed]]
+                   [--save_alpha] [--save_depth]
 
 A config may carry an optional top-level ``particle_filling`` record (not in
 the reference's main.py; PhysGaussian's internal filling): the simulatable
@@ -11,6 +12,18 @@ sources + filled particles.  Without it nothing changes.
 means only; with --save_pcd_deformed (not in the reference) the file is the
 deformed state as any 3DGS tool reads it: scales and rotations of the deformed
 covariances, SH rotated under --rotate_sh, filled particles included.
+--save_alpha and --save_depth (not in the reference, which renders the
+simulated Gaussians alone over a flat background) write what a compositor
+needs to put them back over something else.  --save_alpha: the frames are RGBA
+PNGs, RGB exactly as rendered over the chosen background (to8b, the bytes of a
+run without the flag) and A = alpha8(alpha), alpha = 1 - T_final of the blend
+rounded to the nearest of 256 levels; with the default black background the
+colour is therefore premultiplied by alpha (composite as rgb + (1 - A) *
+behind), with --white_background it is already composited over white.  --save_depth:
+<output_path>/depth/%04d.npy, f32 [H,W], the blend's depth sum z_i alpha_i T_i
+divided by alpha (view-space z, the camera's forward axis) where alpha >= 1/255
+and 0 elsewhere.  Without the flags the same files with the same bytes are
+written as before (configs/lego-matte.json sets both).
 
 Same pipeline as main.py:164-335 of the reference: load Gaussians, sim-area
 mask (inclusive bounds), world2grid, orbit camera (az 130, el 10, r 5.75, F16),
@@ -115,8 +128,11 @@ def modify_cam(cam: TinyCam, center_view_world_space, observant_coordinates, dev
 
 
 def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, bg_color, args, rotation_matrices,
-                 pos_center, scaling_modifier=1.0, to_host=True, sh_rotations=None, shs=None, opacities=None):
+                 pos_center, scaling_modifier=1.0, to_host=True, sh_rotations=None, shs=None, opacities=None,
+                 depth_alpha=False):
     """main.py:108-157 (render-space transform with scaling_modifier = 1.0).
+    depth_alpha (--save_alpha / --save_depth; not in the reference): return
+    (image, depth [H,W], alpha [H,W]) device tensors instead of the image.
     sh_rotations (--rotate_sh; not in the reference): the per-Gaussian view-direction
     rotations for the render-space means, MPM_Simulator.sh_rotations(A).
     shs / opacities: per-particle values when the particles are not pc's masked
@@ -130,9 +146,13 @@ def render_frame(cam: TinyCam, pc: GaussianModel, mask, sim_means3D, sim_covs, b
     means3D = apply_inverse_rotations(undotransform2origin(undoshift2center111(sim_means3D), scaling_modifier,
                                                            pos_center), rotation_matrices)
     covs = apply_inverse_cov_rotations(sim_covs / (scaling_modifier * scaling_modifier), rotation_matrices)
-    image, _ = rasterizer(means3D=means3D, means2D=None, shs=pc.get_features[mask] if shs is None else shs,
-                          colors_precomp=None, opacities=pc.get_opacity[mask] if opacities is None else opacities,
-                          scales=None, rotations=None, cov3D_precomp=covs, sh_rotations=sh_rotations)
+    image, _, *maps = rasterizer(means3D=means3D, means2D=None, shs=pc.get_features[mask] if shs is None else shs,
+                                 colors_precomp=None,
+                                 opacities=pc.get_opacity[mask] if opacities is None else opacities, scales=None,
+                                 rotations=None, cov3D_precomp=covs, sh_rotations=sh_rotations,
+                                 return_depth_alpha=depth_alpha)
+    if depth_alpha:
+        return (image, *maps)
     return image.detach().cpu().numpy().transpose(1, 2, 0) if to_host else image
 
 
@@ -151,21 +171,39 @@ def save_frame(frame, save_path, fid, save_seq):
     Image.fromarray(to8b(frame)).save(os.path.join(save_path, f"{fid:04d}.png"))
 
 
+def alpha8(a):
+    """uint8 of an alpha plane, rounded to nearest: uint8(255 * clip(a, 0, 1) + 0.5).
+    Not to8b's truncation: the blend stops before T falls below 1e-4, so a
+    saturated pixel has alpha = 1 - T_final <= 0.9999, which truncation would
+    store as 254 -- a matte whose opaque interior lets 0.4 % of whatever it is
+    composited over shine through.  Rounded, a stopped pixel is 255."""
+    return (255 * np.clip(a, 0, 1) + 0.5).astype(np.uint8)
+
+
 class FrameWriter:
     """main.py:157-161 without the stalls: each rendered image is copied into a
     pinned host buffer on the render's stream (non-blocking) and encoded to PNG
     on a worker thread once its copy event completes, while the GPU already
-    simulates the next frame.  Same files, same frame order."""
+    simulates the next frame.  Same files, same frame order.  The depth and
+    alpha maps of a frame (submit's depth / alpha) travel the same way:
+    save_alpha makes the PNG RGBA with A = alpha8(alpha), depth_path gets
+    %04d.npy = depth / alpha where alpha >= 1/255, else 0."""
 
-    def __init__(self, save_path, save_seq, workers=4):
+    def __init__(self, save_path, save_seq, workers=4, save_alpha=False, depth_path=None):
         from concurrent.futures import ThreadPoolExecutor
         self.path, self.seq = save_path, save_seq
+        self.save_alpha, self.depth_path = save_alpha, depth_path
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.jobs = []
 
-    def submit(self, image, fid):
-        host = torch.empty(image.shape, dtype=image.dtype, pin_memory=True)
-        host.copy_(image, non_blocking=True)
+    def submit(self, image, fid, depth=None, alpha=None):
+        def pinned(t):
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            return h
+        host = pinned(image)
+        host_a = pinned(alpha) if self.save_alpha or self.depth_path else None
+        host_d = pinned(depth) if self.depth_path else None
         ev = torch.cuda.Event()
         ev.record()
         slot = len(self.seq)
@@ -176,7 +214,15 @@ class FrameWriter:
             frame = host.numpy().transpose(1, 2, 0)
             self.seq[slot] = frame
             from PIL import Image
-            Image.fromarray(to8b(frame)).save(os.path.join(self.path, f"{fid:04d}.png"))
+            rgb = to8b(frame)
+            if self.save_alpha:
+                rgb = np.concatenate([rgb, alpha8(host_a.numpy())[..., None]], axis=2)  # RGBA
+            Image.fromarray(rgb).save(os.path.join(self.path, f"{fid:04d}.png"))
+            if self.depth_path:
+                d, a = host_d.numpy(), host_a.numpy()
+                seen = a >= 1.0 / 255.0
+                np.save(os.path.join(self.depth_path, f"{fid:04d}.npy"),
+                        np.where(seen, d / np.where(seen, a, 1.0), 0.0).astype(np.float32))
 
         self.jobs.append(self.pool.submit(work))
 
@@ -234,10 +280,20 @@ def simulate(model_args, sim_args, render_args, fill_args=None):
     # A x sim-space means, A composed here from the scene's rotation matrices.
     rotate_sh = bool(getattr(render_args, "rotate_sh", False))
     sh_A = render_space_rotation(rot) if rotate_sh else None
-    writer = FrameWriter(out_images, seq)
+    save_alpha = bool(getattr(render_args, "save_alpha", False))
+    save_depth = bool(getattr(render_args, "save_depth", False))
+    maps = save_alpha or save_depth  # the rasterizer's depth and alpha maps ride along with every frame
+    out_depth = os.path.join(render_args.output_path, "depth") if save_depth else None
+    if out_depth:
+        os.makedirs(out_depth, exist_ok=True)
+    writer = FrameWriter(out_images, seq, save_alpha=save_alpha, depth_path=out_depth)
+
+    def submit(fid, **kw):
+        out = render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot, pos_center,
+                           to_host=False, shs=fill_shs, opacities=fill_opa, depth_alpha=maps, **kw)
+        writer.submit(*((out[0], fid, out[1], out[2]) if maps else (out, fid)))
     # frame 0 precedes every postprocess: no rotation yet
-    writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot, pos_center,
-                               to_host=False, shs=fill_shs, opacities=fill_opa), 0)
+    submit(0)
     t0 = time.time()
     for fid in range(1, render_args.num_frames + 1):
         for _ in range(sim_args.steps_per_frame):
@@ -264,9 +320,7 @@ def simulate(model_args, sim_args, render_args, fill_args=None):
                 g2._xyz[mask] = sim_means3D[:n_src]  # the original Gaussians only, not the filled particles
             g2.save_ply(os.path.join(render_args.output_path, "point_cloud", f"iteration_{fid}", "point_cloud.ply"))
         sh_rot = solver.sh_rotations(sh_A) if rotate_sh else None
-        writer.submit(render_frame(cam, gaussians, mask, sim_means3D, sim_covs, background, model_args, rot,
-                                   pos_center, to_host=False, sh_rotations=sh_rot, shs=fill_shs,
-                                   opacities=fill_opa), fid)
+        submit(fid, sh_rotations=sh_rot)
         if fid % 10 == 0 or fid == render_args.num_frames:
             el = time.time() - t0
             print(f"frame {fid}/{render_args.num_frames}  {fid / el:.1f} fps (sim+render+png)", flush=True)

@@ -778,6 +778,8 @@ typedef struct {
   float tanfovx, tanfovy;
   int32_t prefiltered;
   const float* sh_rotations; /* [P,9] row-major or NULL */
+  float* aux_depth;          /* [H,W] or NULL (output) */
+  float* aux_alpha;          /* [H,W] or NULL (output) */
 } gsmpm_raster_args;
 /* sh_rotations (no counterpart in the reference, which computes particle_R
  * and renders the harmonics unrotated; PhysGaussian shades a
@@ -794,6 +796,28 @@ typedef struct {
  * sh_degree 0 it is accepted and has no effect.  All three forward forms
  * honour it; the async form bakes the pointer into a captured graph like the
  * others. */
+/* aux_depth, aux_alpha (not in the pre-2024 upstream API, which returns colour
+ * and radii only): two optional per-pixel maps of the forward, caller-owned
+ * device memory, [H,W] f32 each, independent of each other; NULL is off.  A
+ * pixel's blend takes, skips and stops on Gaussians exactly as for the colour
+ * (power > 0 and alpha < 1/255 skip, T < 1e-4 stop, front to back); over the
+ * contributors i it takes,
+ *   aux_depth = sum_i z_i alpha_i T_i   (z_i: the f32 view-space depth the
+ *               preprocess stores and the Gaussians are ordered by; NOT
+ *               normalised, and the background adds nothing),
+ *   aux_alpha = 1 - T_final.
+ * A pixel no Gaussian reaches has 0 in both (P = 0 and K = 0 included); the
+ * normalised depth aux_depth / aux_alpha is the caller's to form.  Every pixel
+ * of a requested map is written whenever out_color is (so not on GSMPM_ESPACE;
+ * an async frame whose flags are set has maps as invalid as its colour).
+ * Forward only: the maps have no gradient, gsmpm_raster_backward ignores the
+ * two fields, and a context that is not forward-only records the same final T
+ * and last contributor, so its colour backward is unchanged.  Both NULL is the
+ * behaviour without the option, on the kernels that ran before it existed
+ * (k_render<false>); otherwise k_render<true> runs, and out_color and
+ * out_radii are bit-identical either way.  All three forward forms honour the
+ * pointers; the async form bakes them into a captured graph like the others.
+ * gsmpm_raster_workspace_size does not depend on them. */
 
 int gsmpm_raster_create(gsmpm_raster** out);
 int gsmpm_raster_destroy(gsmpm_raster* r);
