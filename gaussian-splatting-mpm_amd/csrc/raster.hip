@@ -38,6 +38,8 @@
 //                    contiguous (no global atomics);
 //   k_preprocess_bwd one lane per Gaussian: sums its pair records, then the
 //                    2D-covariance / projection / SH / 3D-covariance adjoints.
+// Both are templates on AUX (gsmpm_raster_backward_aux: the gradients of the
+// depth and alpha maps); AUX = false is the colour-only pair that ran before.
 //
 // sh_rotations (gsmpm_raster_args, opt-in; not in upstream or the reference):
 // k_preprocess<ROT> / k_preprocess_bwd<ROT> evaluate each Gaussian's SH at
@@ -1459,9 +1461,17 @@ __global__ __launch_bounds__(256) void k_ranges32(int L, const unsigned* __restr
 // ------------------------------------------------------------- backward --
 // Per-pixel adjoint of the blend (upstream BACKWARD::renderCUDA), back to
 // front.  Pair record (3 x float4 at the pair's emission index):
-//   (dmean2D.x, dmean2D.y, dconic.a, dconic.b) (dconic.c, dopacity, dR, dG) (dB, 0, 0, 0)
+//   (dmean2D.x, dmean2D.y, dconic.a, dconic.b) (dconic.c, dopacity, dR, dG) (dB, dz, 0, 0)
 // with upstream's conventions: dmean2D w.r.t. NDC (x W/2, H/2), the conic's
 // off-diagonal term halved, alpha's 0.99 clamp not differentiated.
+// dz is written by k_render_bwd<true> only (k_render_bwd<false> stores 0 there):
+// the adjoint of the maps D = sum z_i alpha_i T_i and A = 1 - T_final
+// (gsmpm_raster_backward_aux), with gD = dL/dD and gA = dL/dA per pixel,
+//   dz_i        = sum_pixels alpha_i T_i gD
+//   dL/dalpha_i += T_i (z_i - S^D_i) gD + T_final / (1 - alpha_i) gA
+// S^D_i the depth blended behind i (the accum recursion of the colours); the
+// alpha map enters as a background of -gA.  z_i is k_preprocess's f32 view
+// depth, the value the forward blended.
 constexpr int kRec = 9;
 #ifndef GSMPM_RBWD_DPP
 #define GSMPM_RBWD_DPP 1  // 0: __shfl_xor wave sums (A/B)
@@ -1505,6 +1515,7 @@ __global__ __launch_bounds__(256) void k_poison_listed(const uint2* __restrict__
   }
 }
 
+template <bool AUX>
 __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__ ranges,
                                                        const unsigned* __restrict__ pos_sorted,
                                                        const unsigned* __restrict__ ids, int W, int H, int gx,
@@ -1512,11 +1523,16 @@ __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__
                                                        const float4* __restrict__ rgbo, const float* __restrict__ bg,
                                                        const float* __restrict__ final_T,
                                                        const int* __restrict__ n_contrib,
-                                                       const float* __restrict__ dL_dpix, float4* __restrict__ rec) {
+                                                       const float* __restrict__ dL_dpix, float4* __restrict__ rec,
+                                                       const float* __restrict__ depth,
+                                                       const float* __restrict__ dL_ddepth,
+                                                       const float* __restrict__ dL_dalpha_map) {
+  constexpr int NR = AUX ? kRec + 1 : kRec;  // AUX: component 9 is dz
   __shared__ float2 s_xy[kBlock];
   __shared__ float4 s_co[kBlock];
   __shared__ float4 s_rgb[kBlock];
-  __shared__ float s_part[kBlock / 64][kRec][kBlock];
+  __shared__ float s_z[AUX ? kBlock : 1];
+  __shared__ float s_part[kBlock / 64][NR][kBlock];
   __shared__ int s_maxlast;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tx = threadIdx.x % kBX, ty = threadIdx.x / kBX;
@@ -1530,7 +1546,15 @@ __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__
   float dpx[3] = {0.f, 0.f, 0.f};
   if (inside)
     for (int ch = 0; ch < 3; ++ch) dpx[ch] = dL_dpix[ch * HW + pix];
-  const float bg_dot = bg[0] * dpx[0] + bg[1] * dpx[1] + bg[2] * dpx[2];
+  float bg_dot = bg[0] * dpx[0] + bg[1] * dpx[1] + bg[2] * dpx[2];
+  float gD = 0.f;
+  if constexpr (AUX) {
+    if (inside) {
+      if (dL_ddepth) gD = dL_ddepth[pix];
+      if (dL_dalpha_map) bg_dot -= dL_dalpha_map[pix];
+    }
+  }
+  float accumD = 0.f, last_z = 0.f;
   if (threadIdx.x == 0) s_maxlast = 0;
   __syncthreads();
   atomicMax(&s_maxlast, last);
@@ -1559,11 +1583,14 @@ __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__
       s_xy[threadIdx.x] = gxy;
       s_co[threadIdx.x] = gco;
       s_rgb[threadIdx.x] = rgbo[id];
+      if constexpr (AUX) s_z[threadIdx.x] = depth[id];
     }
     __syncthreads();
     for (int j = 0; j < nb; ++j) {
       const int contributor = hi - 1 - j;
-      float g[kRec] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float g[NR];
+#pragma unroll
+      for (int q = 0; q < NR; ++q) g[q] = 0.f;
       bool act = false;
       if (contributor < last) {
         const float2 gp = s_xy[j];
@@ -1586,6 +1613,13 @@ __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__
               dL_dalpha += (cc[ch] - accum[ch]) * dpx[ch];
               g[6 + ch] = dchannel_dcolor * dpx[ch];
             }
+            if constexpr (AUX) {
+              const float z = s_z[j];
+              accumD = last_alpha * last_z + (1.f - last_alpha) * accumD;
+              last_z = z;
+              dL_dalpha += (z - accumD) * gD;
+              g[kRec] = dchannel_dcolor * gD;
+            }
             dL_dalpha *= T;
             last_alpha = alpha;
             dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
@@ -1605,31 +1639,31 @@ __global__ __launch_bounds__(kBlock) void k_render_bwd(const uint2* __restrict__
 #if GSMPM_RBWD_DPP
       if (__ballot(act)) {
 #pragma unroll
-        for (int q = 0; q < kRec; ++q) g[q] = wave_total63(g[q]);
+        for (int q = 0; q < NR; ++q) g[q] = wave_total63(g[q]);
       }
       if (lane == 63)
 #pragma unroll
-        for (int q = 0; q < kRec; ++q) s_part[wave][q][j] = g[q];
+        for (int q = 0; q < NR; ++q) s_part[wave][q][j] = g[q];
 #else
       if (__ballot(act)) {
 #pragma unroll
-        for (int q = 0; q < kRec; ++q) g[q] = wave_sum(g[q]);
+        for (int q = 0; q < NR; ++q) g[q] = wave_sum(g[q]);
       }
       if (lane == 0)
 #pragma unroll
-        for (int q = 0; q < kRec; ++q) s_part[wave][q][j] = g[q];
+        for (int q = 0; q < NR; ++q) s_part[wave][q][j] = g[q];
 #endif
     }
     __syncthreads();
     if ((int)threadIdx.x < nb) {
       const int j = threadIdx.x;
-      float o[kRec];
+      float o[NR];
 #pragma unroll
-      for (int q = 0; q < kRec; ++q) o[q] = s_part[0][q][j] + s_part[1][q][j] + s_part[2][q][j] + s_part[3][q][j];
+      for (int q = 0; q < NR; ++q) o[q] = s_part[0][q][j] + s_part[1][q][j] + s_part[2][q][j] + s_part[3][q][j];
       float4* r = rec + (size_t)pos_sorted[range.x + myp] * 3;
       r[0] = make_float4(o[0], o[1], o[2], o[3]);
       r[1] = make_float4(o[4], o[5], o[6], o[7]);
-      r[2] = make_float4(o[8], 0.f, 0.f, 0.f);
+      r[2] = make_float4(o[8], AUX ? o[NR - 1] : 0.f, 0.f, 0.f);
     }
   }
 }
@@ -1773,7 +1807,9 @@ __device__ void cov3d_backward(const float* s, float mod, const float* rot, cons
 }
 
 // computeCov2DCUDA + preprocessCUDA backward, one lane per Gaussian.
-template <bool ROT>
+// AUX: also sums the pairs' dz (record slot r[2].y, k_render_bwd<true>) and adds its chain term
+// through z = vm[2] x + vm[6] y + vm[10] z + vm[14] to dL/dmeans3D.
+template <bool ROT, bool AUX>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* __restrict__ radii,
                                                         const unsigned* __restrict__ offsets,
                                                         const float4* __restrict__ rgbo, const float4* __restrict__ rec,
@@ -1781,6 +1817,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* 
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= a.P) return;
   float g[kRec] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float gz = 0.f;
   float dm[3] = {0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool on = radii[idx] > 0;
   const float* m = a.means3D + (size_t)idx * 3;
@@ -1793,6 +1830,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* 
       g[0] += r0.x; g[1] += r0.y; g[2] += r0.z; g[3] += r0.w;
       g[4] += r1.x; g[5] += r1.y; g[6] += r1.z; g[7] += r1.w;
       g[8] += r2.x;
+      if constexpr (AUX) gz += r2.y;
     }
     if (a.cov3D_precomp) {
       c3 = a.cov3D_precomp + (size_t)idx * 6;
@@ -1868,6 +1906,11 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(RasterDev a, const int* 
     dm[0] += (pm[0] * mw - pm[3] * mul1) * g[0] + (pm[1] * mw - pm[3] * mul2) * g[1];
     dm[1] += (pm[4] * mw - pm[7] * mul1) * g[0] + (pm[5] * mw - pm[7] * mul2) * g[1];
     dm[2] += (pm[8] * mw - pm[11] * mul1) * g[0] + (pm[9] * mw - pm[11] * mul2) * g[1];
+    if constexpr (AUX) {
+      dm[0] += vm[2] * gz;
+      dm[1] += vm[6] * gz;
+      dm[2] += vm[10] * gz;
+    }
   }
   if (a.shs) {
     if (on) {
@@ -2836,6 +2879,15 @@ int gsmpm_raster_backward_rot(gsmpm_raster* r, const gsmpm_raster_args* in, cons
                               const float* dL_dcolor, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                               float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                               float* dL_drotations, float* dL_dsh_rotations, void* stream) {
+  return gsmpm_raster_backward_aux(r, in, radii, dL_dcolor, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
+                                   dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dsh_rotations, stream);
+}
+
+int gsmpm_raster_backward_aux(gsmpm_raster* r, const gsmpm_raster_args* in, const int32_t* radii,
+                              const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                              float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
+                              float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                              float* dL_dsh_rotations, void* stream) {
   GSMPM_REQUIRE(r && in && radii && dL_dcolor && dL_dmeans2D && dL_dcolors && dL_dopacity && dL_dmeans3D && dL_dcov3D,
                 "gsmpm_raster_backward: null argument");
   GSMPM_REQUIRE(r->P == in->P && r->W == in->W && r->H == in->H,
@@ -2884,14 +2936,19 @@ int gsmpm_raster_backward_rot(gsmpm_raster* r, const gsmpm_raster_args* in, cons
                        (const unsigned*)r->vals_sorted, r->rec);
     GSMPM_LAUNCH_CHECK();
   }
+  // the AUX pair runs only when a map gradient is given: a colour-only backward launches the
+  // kernels it always did.  r->depth still holds the forward's view depths (nothing after
+  // k_preprocess writes it), whether or not that forward wrote the maps
+  const bool aux = dL_ddepth || dL_dalpha;
   if (K > 0)
-    hipLaunchKernelGGL(k_render_bwd, dim3(r->gx, r->gy), dim3(kBlock), 0, st, r->ranges, r->vals_sorted,
-                       r->ids_sorted, a.W, a.H, r->gx, r->xy, r->conic, r->rgb, in->bg, r->final_T, r->n_contrib,
-                       dL_dcolor, r->rec);
+    hipLaunchKernelGGL(aux ? k_render_bwd<true> : k_render_bwd<false>, dim3(r->gx, r->gy), dim3(kBlock), 0, st,
+                       r->ranges, r->vals_sorted, r->ids_sorted, a.W, a.H, r->gx, r->xy, r->conic, r->rgb, in->bg,
+                       r->final_T, r->n_contrib, dL_dcolor, r->rec, (const float*)r->depth, dL_ddepth, dL_dalpha);
   RasterGrads o{dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
                 dL_dsh_rotations};
-  hipLaunchKernelGGL(a.sh_rot ? k_preprocess_bwd<true> : k_preprocess_bwd<false>, dim3(div_up(a.P, 256)), dim3(256), 0,
-                     st, a, radii, r->offsets, r->rgb, r->rec, o);
+  auto kpb = aux ? (a.sh_rot ? k_preprocess_bwd<true, true> : k_preprocess_bwd<false, true>)
+                 : (a.sh_rot ? k_preprocess_bwd<true, false> : k_preprocess_bwd<false, false>);
+  hipLaunchKernelGGL(kpb, dim3(div_up(a.P, 256)), dim3(256), 0, st, a, radii, r->offsets, r->rgb, r->rec, o);
   GSMPM_LAUNCH_CHECK();
   return GSMPM_OK;
 }

@@ -18,6 +18,13 @@ Differences, each deliberate:
     and ground-truth frames rendered from the same simulator at --E_true.
     The on-disk loaders (camera.json, frame.json, physical.json, PNGs,
     static_gaussians/point_cloud.ply, init_velocity.json) are kept for real data.
+  * --lambda_alpha L (default 0: the reference's colour-only loss, on the
+    kernels and with the history it always had) adds a silhouette term
+    L * l1_loss(alpha, gt_alpha) to both losses: alpha = 1 - T_final from the
+    rasterizer (return_depth_alpha, depth_alpha_grad), gt_alpha the frame's
+    mask (an RGBA frame's fourth channel, or the synthetic ground truth's
+    rendered alpha).  It keeps a colour-only fit from fading the object into
+    the background.
 """
 from __future__ import annotations
 
@@ -72,6 +79,7 @@ class SystemIndentifier:
         self.sim_args = sim_args
         self.args = args
         self.total_iters = getattr(args, "iters", total_iters)
+        self.lambda_alpha = float(getattr(args, "lambda_alpha", 0.0))
         self.image_bg_cuda = _bg_cuda()
         if synthetic is not None:
             self.synthesize(**synthetic)
@@ -88,8 +96,10 @@ class SystemIndentifier:
         with open(os.path.join(data_path, "camera.json"), "r") as cam_file:
             cameras = json.load(cam_file)
         cam_infos_all = []
+        alphas_all = []  # per frame, per camera: the image's fourth channel in [0, 1] (lambda_alpha > 0 only)
         for frame_id in range(train_num_frames + test_num_frames):
             cam_infos = []
+            alphas_all.append([])
             for cam_id, camera in enumerate(cameras):
                 intrinsic = np.array(camera["K"])
                 c2w = deepcopy(np.array(camera["c2w"]))
@@ -101,8 +111,15 @@ class SystemIndentifier:
                 FovY = focal2fov(intrinsic[1][1], image_height)
                 cam_name = camera["camera"]
                 image_path = os.path.join(data_path, cam_name, f"{frame_id:03}.png")
-                im_data = np.array(Image.open(image_path).convert("RGBA"))
+                pil = Image.open(image_path)
+                if self.lambda_alpha > 0:
+                    if "A" not in pil.getbands():
+                        raise ValueError(f"--lambda_alpha {self.lambda_alpha} needs an alpha channel in every frame, "
+                                         f"but {image_path} has none (mode {pil.mode})")
+                im_data = np.array(pil.convert("RGBA"))
                 norm_data = im_data / 255.0
+                if self.lambda_alpha > 0:
+                    alphas_all[-1].append(norm_data[:, :, 3].astype(np.float32))
                 arr = norm_data[:, :, :3] * norm_data[:, :, 3:4] + image_bg * (1 - norm_data[:, :, 3:4])
                 image = Image.fromarray(np.array(arr * 255.0, dtype=np.byte), "RGB")
                 cam_infos.append(CameraInfo(uid=cam_id, R=R, T=T, FovY=FovY, FovX=FovX, image=image,
@@ -117,6 +134,8 @@ class SystemIndentifier:
                 gt_image = PILtoTorch(c.image, (image_width, image_height))[:3, ...]
                 camera_list.append(Camera(colmap_id=c.uid, R=c.R, T=c.T, FoVx=c.FovX, FoVy=c.FovY, image=gt_image,
                                           gt_alpha_mask=None, image_name=c.image_name, uid=cid, data_device="cuda"))
+                if self.lambda_alpha > 0:  # not Camera(gt_alpha_mask=...), which multiplies the image
+                    camera_list[-1].gt_alpha = torch.from_numpy(alphas_all[frame_id][cid]).cuda()
             self.cameras_all.append(camera_list)
         self.dt = []
         with open(os.path.join(data_path, "frame.json"), "r") as file:
@@ -198,7 +217,11 @@ class SystemIndentifier:
                 frame = []
                 for cam in base:
                     img = self.render(cam, self.gaussians, means, covs)
+                    if self.lambda_alpha > 0:
+                        img, alpha = img
                     frame.append(mk(cam.R, cam.T, img.detach().cpu(), f"{cam.image_name}_{fid:03d}", cam.uid))
+                    if self.lambda_alpha > 0:  # not Camera(gt_alpha_mask=...), which multiplies the image
+                        frame[-1].gt_alpha = alpha.detach().clone()
                 self.cameras_all.append(frame)
         self.E_true, self.nu_true = E_true, sa.nu
 
@@ -225,7 +248,11 @@ class SystemIndentifier:
                 gt_image = viewpoint_cam.original_image
                 if fid == 0:  # optimize the Gaussians' appearance
                     rendered_image = self.render(viewpoint_cam, self.gaussians, sim_means3D, sim_covs)
+                    if self.lambda_alpha > 0:
+                        rendered_image, rendered_alpha = rendered_image
                     loss = 0.8 * l1_loss(rendered_image, gt_image) + 0.2 * ssim(rendered_image, gt_image)
+                    if self.lambda_alpha > 0:
+                        loss = loss + self.lambda_alpha * l1_loss(rendered_alpha, viewpoint_cam.gt_alpha)
                     loss.backward()
                     self.gaussians.optimizer.step()
                     self.gaussians.optimizer.zero_grad(set_to_none=True)
@@ -237,7 +264,11 @@ class SystemIndentifier:
                     mpm_sim_covs = mpm_solver.mpm_state.particle_cov.to_torch().cuda().requires_grad_(True)
                     sim_means3D, sim_covs = self.grid2world(mpm_sim_means3D, mpm_sim_covs, self.sim_args)
                     rendered_image = self.render(viewpoint_cam, self.gaussians, sim_means3D, sim_covs)
+                    if self.lambda_alpha > 0:
+                        rendered_image, rendered_alpha = rendered_image
                     loss = 0.8 * l1_loss(rendered_image, gt_image) + 0.2 * ssim(rendered_image, gt_image)
+                    if self.lambda_alpha > 0:
+                        loss = loss + self.lambda_alpha * l1_loss(rendered_alpha, viewpoint_cam.gt_alpha)
                     loss.backward()
                     mpm_solver.clear_grads()
                     mpm_solver.mpm_state.set_grads(mpm_sim_means3D.grad.cpu().numpy().astype(np.float32),
@@ -254,7 +285,7 @@ class SystemIndentifier:
         return history
 
     def render(self, viewpoint_camera, pc, sim_means3D, sim_covs):
-        """extra.py:260-305."""
+        """extra.py:260-305.  With lambda_alpha > 0: (image, alpha [H,W]), the alpha map in the graph."""
         screenspace_points = torch.zeros_like(pc.get_xyz, dtype=pc.get_xyz.dtype, requires_grad=True,
                                               device="cuda") + 0
         try:
@@ -269,6 +300,13 @@ class SystemIndentifier:
             viewmatrix=viewpoint_camera.world_view_transform, projmatrix=viewpoint_camera.full_proj_transform,
             sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
         rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+        if self.lambda_alpha > 0:
+            rendered_image, _, _, alpha = rasterizer(means3D=sim_means3D, means2D=screenspace_points,
+                                                     shs=pc.get_features, colors_precomp=None,
+                                                     opacities=pc.get_opacity, scales=None, rotations=None,
+                                                     cov3D_precomp=sim_covs, return_depth_alpha=True,
+                                                     depth_alpha_grad=True)
+            return rendered_image, alpha
         rendered_image, _ = rasterizer(means3D=sim_means3D, means2D=screenspace_points, shs=pc.get_features,
                                        colors_precomp=None, opacities=pc.get_opacity, scales=None, rotations=None,
                                        cov3D_precomp=sim_covs)
@@ -309,6 +347,8 @@ if __name__ == "__main__":
     parser.add_argument("--E_true", type=float, default=1e5)
     parser.add_argument("--image_size", type=int, default=256)
     parser.add_argument("--iters", type=int, default=total_iters)
+    parser.add_argument("--lambda_alpha", type=float, default=0.0,
+                        help="weight of the silhouette term l1(alpha, gt_alpha) in both losses (0: colour only)")
     sim_args = MPMParams(parser)
     args = parser.parse_args()
     for k in ("E", "nu", "density", "n_grid", "grid_extent"):  # CLI overrides of the MPMParams group

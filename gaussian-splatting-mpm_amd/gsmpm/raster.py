@@ -225,11 +225,15 @@ def _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, 
     return a, keep
 
 
-def backward(context, keep, a, radii, grad_color):
+def backward(context, keep, a, radii, grad_color, grad_depth=None, grad_alpha=None):
     """gsmpm_raster_backward_rot on the state of `context`'s forward.  Returns a dict of
     means2D [P,3], colors [P,3], opacity [P], means3D [P,3], cov3D [P,6],
     sh [P,M,3] | None, scales [P,3] | None, rotations [P,4] | None,
-    sh_rotations [P,3,3] | None (when the forward had sh_rotations)."""
+    sh_rotations [P,3,3] | None (when the forward had sh_rotations).
+    grad_depth / grad_alpha [H,W]: the gradients of the forward's depth and
+    alpha maps (gsmpm_raster_backward_aux; either may be None = zero, and the
+    forward need not have returned the maps).  With both None the call is the
+    colour backward it always was."""
     dev = keep["means3D"].device
     P = a.P
     z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -239,6 +243,22 @@ def backward(context, keep, a, radii, grad_color):
          "rotations": z(P, 4) if keep["rotations"] is not None else None,
          "sh_rotations": z(P, 3, 3) if keep.get("sh_rotations") is not None else None}
     grad_color = grad_color.detach().to(torch.float32).contiguous()
+    if grad_depth is not None or grad_alpha is not None:
+        maps = []
+        for name, m in (("grad_depth", grad_depth), ("grad_alpha", grad_alpha)):
+            if m is not None:
+                if tuple(m.shape) != (a.H, a.W):
+                    raise ValueError(f"backward: {name} must be [{a.H},{a.W}], got {tuple(m.shape)}")
+                m = m.detach().to(device=dev, dtype=torch.float32).contiguous()
+            maps.append(m)
+        with torch.cuda.device(dev):
+            check(LIB.gsmpm_raster_backward_aux(context.h, ctypes.byref(a), ptr(radii), ptr(grad_color),
+                                                ptr(maps[0]), ptr(maps[1]),
+                                                ptr(g["means2D"]), ptr(g["colors"]), ptr(g["opacity"]),
+                                                ptr(g["means3D"]), ptr(g["cov3D"]), ptr(g["sh"]), ptr(g["scales"]),
+                                                ptr(g["rotations"]), ptr(g["sh_rotations"]), stream_of(dev)),
+                  "rasterize_gaussians_backward (depth/alpha)")
+        return g
     with torch.cuda.device(dev):
         check(LIB.gsmpm_raster_backward_rot(context.h, ctypes.byref(a), ptr(radii), ptr(grad_color),
                                             ptr(g["means2D"]), ptr(g["colors"]), ptr(g["opacity"]), ptr(g["means3D"]),
@@ -262,7 +282,8 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height
     the view direction d (include/gsmpm.h, gsmpm_raster_args.sh_rotations).
     depth / alpha: new f32 tensors holding D = sum z_i alpha_i T_i (view-space
     depth, not normalised) and A = 1 - T_final of the colour blend
-    (gsmpm_raster_args.aux_depth / aux_alpha); no gradient flows to them."""
+    (gsmpm_raster_args.aux_depth / aux_alpha); their gradients go back through
+    `backward`'s grad_depth / grad_alpha."""
     dev = means3D.device
     a, keep = _args(means3D, opacities, viewmatrix, projmatrix, campos, bg, image_height, image_width, tanfovx,
                     tanfovy, sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier,

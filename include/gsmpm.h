@@ -810,9 +810,11 @@ typedef struct {
  * normalised depth aux_depth / aux_alpha is the caller's to form.  Every pixel
  * of a requested map is written whenever out_color is (so not on GSMPM_ESPACE;
  * an async frame whose flags are set has maps as invalid as its colour).
- * Forward only: the maps have no gradient, gsmpm_raster_backward ignores the
- * two fields, and a context that is not forward-only records the same final T
- * and last contributor, so its colour backward is unchanged.  Both NULL is the
+ * Their gradients go in through gsmpm_raster_backward_aux (dL_ddepth,
+ * dL_dalpha); every backward ignores the two fields themselves, and a context
+ * that is not forward-only records the same final T and last contributor with
+ * or without them, so its colour backward is unchanged.  The workspace and
+ * async forms stay forward-only.  Both NULL is the
  * behaviour without the option, on the kernels that ran before it existed
  * (k_render<false>); otherwise k_render<true> runs, and out_color and
  * out_radii are bit-identical either way.  All three forward forms honour the
@@ -845,6 +847,29 @@ int gsmpm_raster_backward_rot(gsmpm_raster* r, const gsmpm_raster_args* a, const
                               const float* dL_dcolor, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                               float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                               float* dL_drotations, float* dL_dsh_rotations, void* stream);
+/* The same with the gradients of the two maps of the forward (aux_depth,
+ * aux_alpha above): dL_ddepth = dL/dD and dL_dalpha = dL/dA, [H,W] f32 each,
+ * either may be NULL (= zero).  Over a pixel's contributors i, with T_i the
+ * transmittance in front of i and S^D_i the depth blended behind it,
+ *   dL/dz_i     += alpha_i T_i dL/dD,
+ *   dL/dalpha_i += T_i (z_i - S^D_i) dL/dD + T_final / (1 - alpha_i) dL/dA
+ * (the alpha map enters as a background of -dL/dA), and z_i = vm[2] x + vm[6] y
+ * + vm[10] z + vm[14] adds (vm[2], vm[6], vm[10]) sum dL/dz_i to dL_dmeans3D;
+ * z_i is the f32 view depth the forward stored.  Upstream's conventions hold
+ * (the 0.99 clamp is straight-through; no gradient to the camera matrices).
+ * Uses the state of the context's last forward whether or not that forward
+ * wrote the maps (a->aux_depth / aux_alpha are ignored here).  Outputs and
+ * their rules as gsmpm_raster_backward_rot, which forwards here with both
+ * NULL: then the kernels of the colour backward run (k_render_bwd<false>) and
+ * the result is bit-identical to it; with a map gradient k_render_bwd<true>
+ * and the matching k_preprocess_bwd run.  A forward-only context fails;
+ * P = 0 returns GSMPM_OK and writes nothing; a frame that bins no pair writes
+ * zeros. */
+int gsmpm_raster_backward_aux(gsmpm_raster* r, const gsmpm_raster_args* a, const int32_t* radii,
+                              const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                              float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D,
+                              float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                              float* dL_dsh_rotations, void* stream);
 /* Forward-only context (on != 0): gsmpm_raster_forward skips the per-pixel
  * state (final T, last contributor: 8 B a pixel) that only a backward reads,
  * and gsmpm_raster_backward on it fails.  Used for main.py's frames

@@ -2,7 +2,11 @@
 path) on the lego frame (100k Gaussians, 800x800, SH degree 3, precomputed
 covariances as main.py/extra.py pass them), REPS iterations, for timing and
 rocprofv3 --kernel-trace --stats.  Prints ms per forward and per
-forward + backward."""
+forward + backward.  AUX=1: then the same iterations with a loss that also
+uses the alpha and depth maps (return_depth_alpha, depth_alpha_grad:
+k_render_bwd<true> and the AUX k_preprocess_bwd instead of the colour-only
+pair), and the C backward alone (gsmpm.raster.backward) timed with events,
+colour-only against colour + both maps."""
 import math
 import os
 import sys
@@ -25,6 +29,7 @@ class A:
 
 
 REPS = int(os.environ.get('REPS', 20))
+AUX = os.environ.get('AUX', '0') == '1'
 dev = torch.device('cuda:0')
 scene = bench.build_scene(A, dev)
 sim, specs = bench.make_sim(scene, dev)
@@ -76,3 +81,40 @@ torch.cuda.synchronize()
 t2 = time.perf_counter()
 print(f"forward (no grad) {(t1 - t0) / REPS * 1e3:.3f} ms; forward+backward with the L1 loss "
       f"{(t2 - t1) / REPS * 1e3:.3f} ms per iteration ({REPS} reps)")
+
+if AUX:
+    from gsmpm import raster  # noqa: E402
+    tgt_a = torch.rand(cam.height, cam.width, device=dev)
+    tgt_d = 4.0 * torch.rand(cam.height, cam.width, device=dev)
+
+    def step_aux():
+        img, _, depth, alpha = ras(means3D=m3, means2D=None, shs=sh, colors_precomp=None, opacities=op, scales=None,
+                                   rotations=None, cov3D_precomp=c6, return_depth_alpha=True, depth_alpha_grad=True)
+        ((img - target).abs().mean() + (alpha - tgt_a).abs().mean() + (depth - tgt_d).abs().mean()).backward()
+
+    for _ in range(3):
+        step_aux()
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    for _ in range(REPS):
+        step_aux()
+    torch.cuda.synchronize()
+    t4 = time.perf_counter()
+    print(f"forward+backward with the L1 loss on colour, alpha and depth {(t4 - t3) / REPS * 1e3:.3f} ms per iteration")
+    # the C backward alone on one kept forward
+    ctx = raster.RasterContext()
+    out = raster.forward(m3, op.reshape(-1), st.viewmatrix, st.projmatrix, st.campos, st.bg, cam.height, cam.width,
+                         st.tanfovx, st.tanfovy, sh_degree=3, shs=sh, cov3D_precomp=c6, context=ctx, return_args=True)
+    a, keep = out[-2:]
+    gC = torch.randn(3, cam.height, cam.width, device=dev)
+    gD, gA = torch.randn(cam.height, cam.width, device=dev), torch.randn(cam.height, cam.width, device=dev)
+    for label, extra in (("colour only", ()), ("colour + depth + alpha", (gD, gA))):
+        for _ in range(3):
+            raster.backward(ctx, keep, a, out[2], gC, *extra)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(REPS):
+            raster.backward(ctx, keep, a, out[2], gC, *extra)
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"gsmpm_raster_backward ({label}) {e0.elapsed_time(e1) / REPS:.3f} ms per call")
